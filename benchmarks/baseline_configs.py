@@ -50,7 +50,7 @@ def main() -> int:
     lines = []
     for name, flags in CONFIGS:
         cmd = [sys.executable, str(REPO / "bench.py"),
-               "--steps", str(args.steps), "--warmup", str(args.warmup)] + flags
+               "--steps", str(args.steps), "--warmup", str(args.warmup), "--full"] + flags
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=900,
                              cwd=REPO)
         if out.returncode != 0:

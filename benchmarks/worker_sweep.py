@@ -34,7 +34,7 @@ def main() -> int:
         proc = subprocess.run(
             [sys.executable, str(REPO / "bench.py"), "--crs", str(args.crs),
              "--steps", str(args.steps), "--warmup", str(args.warmup),
-             "--workers", str(w)],
+             "--workers", str(w), "--full"],
             capture_output=True, text=True, cwd=REPO,
         )
         if proc.returncode != 0:
