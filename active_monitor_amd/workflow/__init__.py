@@ -6,6 +6,7 @@ from .engines import (
     always_succeed,
     never_complete,
 )
+from .validate import validate_workflow_spec
 
 __all__ = [
     "LocalWorkflowEngine",
@@ -13,4 +14,5 @@ __all__ = [
     "always_fail",
     "always_succeed",
     "never_complete",
+    "validate_workflow_spec",
 ]

@@ -1,0 +1,203 @@
+"""Offline workflow tools: ``python -m active_monitor_amd.workflow``.
+
+``lint FILE...``
+    Check Workflow or HealthCheck YAML against the surface the local executor
+    supports. For a HealthCheck the inline check and remedy workflows are
+    linted. Prints one line per problem; exit status 1 when there are any.
+
+``run FILE [-p name=value ...] [--remedy]``
+    Execute one workflow with the local executor against a throw-away
+    in-memory store and print the phase and a node table. For a HealthCheck
+    the check workflow runs (``--remedy``: the remedy workflow). Exit status
+    0 for ``Succeeded``, 1 for ``Failed``.
+
+Neither needs a server.
+"""
+from __future__ import annotations
+
+import argparse
+import asyncio
+import sys
+from typing import Any, Dict, Iterator, List, Optional, Tuple
+
+import yaml
+
+from ..api.types import HealthCheck
+from ..engine.parse import (
+    WorkflowParseError,
+    parse_remedy_workflow_from_healthcheck,
+    parse_workflow_from_healthcheck,
+)
+from ..kube import MemoryApiServer, MemoryClient
+from ..kube.registry import WF_API_VERSION, WF_KIND
+from . import LocalWorkflowEngine, validate_workflow_spec
+
+
+def _inline(wf: Any) -> bool:
+    return (
+        wf is not None and wf.resource is not None
+        and wf.resource.source is not None
+        and wf.resource.source.inline is not None
+    )
+
+
+def _specs(path: str) -> Iterator[Tuple[str, Optional[Dict[str, Any]], List[str]]]:
+    """``(label, spec, problems)`` for every workflow found in ``path``."""
+    try:
+        with open(path) as f:
+            docs = [d for d in yaml.safe_load_all(f) if d is not None]
+    except (OSError, yaml.YAMLError) as e:
+        yield path, None, [str(e)]
+        return
+    for i, doc in enumerate(docs):
+        label = path if len(docs) == 1 else f"{path}[{i}]"
+        kind = doc.get("kind") if isinstance(doc, dict) else None
+        if kind == "Workflow":
+            spec = doc.get("spec")
+            yield label, spec, [] if isinstance(spec, dict) else ["invalid workflow, missing spec"]
+        elif kind == "HealthCheck":
+            try:
+                hc = HealthCheck.from_dict(doc)
+            except Exception as e:
+                yield label, None, [f"invalid HealthCheck: {e}"]
+                continue
+            found = False
+            for what, wf, parse in (
+                ("workflow", hc.spec.workflow, parse_workflow_from_healthcheck),
+                ("remedyworkflow", hc.spec.remedy_workflow,
+                 parse_remedy_workflow_from_healthcheck),
+            ):
+                if not _inline(wf):
+                    continue
+                found = True
+                try:
+                    spec, _ = parse(hc)
+                    yield f"{label} ({what})", spec, []
+                except WorkflowParseError as e:
+                    yield f"{label} ({what})", None, [str(e)]
+            if not found:
+                yield label, None, []  # file/URL sources: nothing to lint offline
+        else:
+            yield label, None, [f"expected kind Workflow or HealthCheck, found {kind!r}"]
+
+
+def lint(paths: List[str]) -> int:
+    bad = 0
+    for path in paths:
+        for label, spec, problems in _specs(path):
+            if spec is not None and not problems:
+                problems = validate_workflow_spec(spec)
+            for p in problems:
+                print(f"{label}: {p}")
+            bad += len(problems)
+    if not bad:
+        print("ok")
+    return 1 if bad else 0
+
+
+async def _execute(spec: Dict[str, Any], name: str) -> Dict[str, Any]:
+    client = MemoryClient(MemoryApiServer())
+    engine = LocalWorkflowEngine(client, ttl_seconds=None)
+    sub = client.watch(WF_API_VERSION, WF_KIND, "local")
+    await engine.start()
+    try:
+        await client.create({
+            "apiVersion": WF_API_VERSION, "kind": WF_KIND,
+            "metadata": {"name": name, "namespace": "local"}, "spec": spec,
+        })
+        async for ev in sub:
+            status = ev["object"].get("status") or {}
+            if status.get("phase") in ("Succeeded", "Failed"):
+                return status
+    finally:
+        sub.close()
+        await engine.stop()
+    raise RuntimeError("workflow watch ended before the workflow did")
+
+
+def _print_nodes(status: Dict[str, Any]) -> None:
+    nodes = status.get("nodes") or {}
+    if not nodes:
+        return
+    child_ids = {c for n in nodes.values() for c in n.get("children", [])}
+    rows: List[Tuple[str, str, str, str]] = []
+
+    def walk(node_id: str, depth: int) -> None:
+        n = nodes[node_id]
+        rows.append(("  " * depth + n["displayName"], n["type"], n.get("phase", ""),
+                     " ".join((n.get("message") or "").split())[:100]))
+        for c in n.get("children", []):
+            if c in nodes:
+                walk(c, depth + 1)
+
+    for node_id in nodes:
+        if node_id not in child_ids:
+            walk(node_id, 0)
+    width = max(len(r[0]) for r in rows + [("NODE", "", "", "")])
+    print(f"{'NODE':<{width}}  {'TYPE':<9}  {'PHASE':<9}  MESSAGE")
+    for name, type_, phase, message in rows:
+        print(f"{name:<{width}}  {type_:<9}  {phase:<9}  {message}".rstrip())
+
+
+def run(path: str, params: List[str], remedy: bool) -> int:
+    wanted = "(remedyworkflow)" if remedy else "(workflow)"
+    found: List[Tuple[str, Dict[str, Any]]] = []
+    for label, spec, problems in _specs(path):
+        if problems:
+            print(f"{label}: {problems[0]}")
+            return 1
+        if spec is not None:
+            found.append((label, spec))
+    # a HealthCheck yields "(workflow)" / "(remedyworkflow)"; a bare Workflow
+    # document has no suffix and is only eligible without --remedy
+    matching = [s for label, s in found if label.endswith(wanted)]
+    if not matching and not remedy:
+        matching = [s for _, s in found]
+    if not matching:
+        print(f"{path}: no inline {'remedy ' if remedy else ''}workflow found")
+        return 1
+    chosen = matching[0]
+    overrides = {}
+    for p in params:
+        name, sep, value = p.partition("=")
+        if not sep:
+            print(f"-p expects name=value, got {p!r}")
+            return 2
+        overrides[name] = value
+    if overrides:
+        args = chosen.setdefault("arguments", {})
+        declared = [q for q in args.get("parameters") or []
+                    if isinstance(q, dict) and q.get("name") not in overrides]
+        args["parameters"] = declared + [{"name": k, "value": v} for k, v in overrides.items()]
+    status = asyncio.run(_execute(chosen, "run"))
+    print(f"phase: {status['phase']}")
+    if status.get("message"):
+        print(f"message: {status['message']}")
+    for p in (status.get("outputs") or {}).get("parameters") or []:
+        print(f"output {p['name']}: {p['value']}")
+    _print_nodes(status)
+    return 0 if status["phase"] == "Succeeded" else 1
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    ap = argparse.ArgumentParser(
+        prog="python -m active_monitor_amd.workflow",
+        description="Lint or run workflows with the local executor; no server needed.",
+    )
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    p_lint = sub.add_parser("lint", help="check Workflow / HealthCheck YAML")
+    p_lint.add_argument("files", nargs="+", metavar="FILE")
+    p_run = sub.add_parser("run", help="execute one workflow locally")
+    p_run.add_argument("file", metavar="FILE")
+    p_run.add_argument("-p", "--parameter", action="append", default=[], metavar="name=value",
+                       help="set or override a spec.arguments parameter")
+    p_run.add_argument("--remedy", action="store_true",
+                       help="for a HealthCheck, run its remedy workflow instead of the check")
+    args = ap.parse_args(argv)
+    if args.cmd == "lint":
+        return lint(args.files)
+    return run(args.file, args.parameter, args.remedy)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -12,14 +12,16 @@ that role in-process:
   policy, the success path — which the reference's envtest never reaches — is
   exercised too.
 - :class:`LocalWorkflowEngine` — actually EXECUTES Argo-shaped workflows as
-  local subprocesses (container/script templates, ``steps`` groups,
-  ``retryStrategy.limit``, ``activeDeadlineSeconds``, output parameters), so
-  the framework can run health checks standalone without a cluster.
+  local subprocesses (container/script leaves, ``steps`` and ``dag``
+  templates, parameters, loops, ``when``, exit handlers, retries with
+  backoff, ``activeDeadlineSeconds``, output parameters), so the framework
+  can run health checks standalone without a cluster. The template walk
+  itself lives in :mod:`.executor`, substitution and ``when`` in
+  :mod:`.template`, static checks in :mod:`.validate`.
 """
 from __future__ import annotations
 
 import asyncio
-import json
 import logging
 import time
 from typing import Any, Callable, Dict, List, Optional, Tuple
@@ -191,16 +193,36 @@ def _now_iso() -> str:
 
 
 class LocalWorkflowEngine(_EngineBase):
-    """Executes Argo-shaped workflows locally.
+    """Executes Argo-shaped workflows locally, one subprocess per leaf.
 
-    Supported template surface (enough to run every example shipped with the
-    framework): ``container`` (command+args as a local subprocess; ``image``
-    is informational without a container runtime), ``script`` (source piped to
-    the command interpreter), ``steps`` (sequential groups of parallel steps),
-    ``retryStrategy.limit``, workflow-level ``activeDeadlineSeconds``, and
-    ``outputs.parameters`` with ``globalName`` surfacing into
-    ``status.outputs.parameters`` (the custom-metrics contract,
-    README.md:275-285).
+    Supported surface (docs/OPERATIONS.md has the full list and what is
+    deliberately absent):
+
+    - ``container`` (command+args run as a local process; ``image`` is
+      informational without a container runtime) and ``script`` (source piped
+      to the interpreter) leaves, with ``env`` name/value pairs; ``suspend``;
+    - ``steps`` (sequential groups of parallel steps) and ``dag`` templates
+      (``dependencies`` / ``depends: "a && b"``, fail-fast by default);
+    - ``withItems`` / ``withParam`` fan-out and ``when`` conditions on steps
+      and tasks;
+    - parameters: ``spec.arguments``, template ``inputs``, ``{{item}}``,
+      ``{{retries}}``, ``{{workflow.*}}`` and ``{{steps|tasks.X.outputs.*}}``,
+      substituted in one pass and never re-split into argv elements;
+    - outputs: ``outputs.result`` (stdout), ``valueFrom.path`` (the leaf then
+      runs in a throw-away working directory), ``valueFrom.parameter`` on
+      composite templates, and ``globalName`` surfacing into
+      ``status.outputs.parameters`` (the custom-metrics contract,
+      README.md:275-285);
+    - ``retryStrategy`` with ``limit`` and ``backoff``;
+    - ``spec.onExit`` with ``{{workflow.status}}``;
+    - workflow-level ``activeDeadlineSeconds``. Every leaf runs in its own
+      process group, which is killed when the deadline passes or the engine
+      stops.
+
+    The spec is checked by :func:`~.validate.validate_workflow_spec` before
+    anything starts. Status is written twice per workflow (``Running``, then
+    the terminal phase); the terminal write carries ``status.nodes``, one
+    entry per step, so a user can see which task of a DAG failed.
     """
 
     def __init__(self, client: KubeClient, namespace: Optional[str] = None,
@@ -208,129 +230,81 @@ class LocalWorkflowEngine(_EngineBase):
         super().__init__(client, namespace, ttl_seconds)
         self.completed = 0
 
+    async def stop(self) -> None:
+        inflight = list(self._inflight.values())
+        await super().stop()
+        # cancelled runs kill and reap their process groups before they end
+        if inflight:
+            await asyncio.gather(*inflight, return_exceptions=True)
+
     async def _run(self, wf: Dict[str, Any]) -> None:
+        from .executor import WorkflowRun
+        from .validate import validate_workflow_spec
+
         spec = wf.get("spec") or {}
         await self._set_status(wf, {"phase": "Running", "startedAt": _now_iso()})
-        deadline = spec.get("activeDeadlineSeconds")
-        try:
-            if deadline:
-                phase, message, outputs = await asyncio.wait_for(
-                    self._run_spec(spec), float(deadline)
-                )
-            else:
-                phase, message, outputs = await self._run_spec(spec)
-        except asyncio.TimeoutError:
-            phase, message, outputs = "Failed", "deadline exceeded", []
-        except asyncio.CancelledError:
-            raise
-        except Exception as e:
-            phase, message, outputs = "Failed", str(e), []
+        nodes: Dict[str, Any] = {}
+        outputs: List[Dict[str, Any]] = []
+        problems = validate_workflow_spec(spec)
+        if problems:
+            phase, message = "Failed", problems[0]
+        else:
+            meta = wf["metadata"]
+            run = WorkflowRun(spec, meta["name"], meta.get("namespace", ""))
+            try:
+                phase, message, timed_out = await self._run_phases(run, spec)
+            except asyncio.CancelledError:
+                run.terminate("engine stopped")
+                raise
+            nodes = run.nodes
+            if not timed_out:  # a run that was cut short publishes no outputs
+                outputs = run.global_outputs
         status: Dict[str, Any] = {"phase": phase, "finishedAt": _now_iso()}
         if message:
             status["message"] = message
         if outputs:
             status["outputs"] = {"parameters": outputs}
+        if nodes:
+            status["nodes"] = nodes
         await self._set_status(wf, status)
         self._schedule_ttl(wf)
         self.completed += 1
 
-    async def _run_spec(self, spec: Dict[str, Any]) -> Tuple[Phase, str, List[Dict[str, Any]]]:
-        templates = {t.get("name"): t for t in spec.get("templates", []) or []}
-        entry = spec.get("entrypoint")
-        if entry not in templates:
-            return "Failed", f"entrypoint {entry!r} not found", []
-        outputs: List[Dict[str, Any]] = []
-        ok, message = await self._run_template(templates, templates[entry], outputs)
-        return ("Succeeded" if ok else "Failed"), message, outputs
+    async def _run_phases(self, run: Any, spec: Dict[str, Any]) -> Tuple[Phase, str, bool]:
+        """The entrypoint, then the exit handler. Each gets the workflow's
+        ``activeDeadlineSeconds`` as a budget of its own, so the handler
+        still runs after the entrypoint used up the deadline. Returns
+        ``(phase, message, timed_out)``."""
+        phase, message, timed_out = await self._bounded(
+            run, run.run_entrypoint(), spec, "deadline exceeded"
+        )
+        if spec.get("onExit"):
+            exit_phase, exit_message, exit_timed_out = await self._bounded(
+                run, run.run_exit_handler(phase), spec, "exit handler: deadline exceeded"
+            )
+            timed_out = timed_out or exit_timed_out
+            if exit_phase == "Failed":
+                if phase != "Failed":
+                    message = exit_message
+                phase = "Failed"
+        return phase, message, timed_out
 
-    async def _run_template(
-        self,
-        templates: Dict[str, Dict[str, Any]],
-        tmpl: Dict[str, Any],
-        outputs: List[Dict[str, Any]],
-    ) -> Tuple[bool, str]:
-        retry_limit = int(((tmpl.get("retryStrategy") or {}).get("limit")) or 0)
-        attempts = retry_limit + 1
-        last_msg = ""
-        for attempt in range(attempts):
-            ok, last_msg = await self._run_template_once(templates, tmpl, outputs)
-            if ok:
-                return True, ""
-        return False, last_msg
-
-    async def _run_template_once(
-        self,
-        templates: Dict[str, Dict[str, Any]],
-        tmpl: Dict[str, Any],
-        outputs: List[Dict[str, Any]],
-    ) -> Tuple[bool, str]:
-        if "steps" in tmpl:
-            for group in tmpl["steps"] or []:
-                steps = group if isinstance(group, list) else [group]
-                results = await asyncio.gather(
-                    *[
-                        self._run_template(
-                            templates, templates.get(s.get("template"), {}), outputs
-                        )
-                        for s in steps
-                        if isinstance(s, dict)
-                    ]
-                )
-                for ok, msg in results:
-                    if not ok:
-                        return False, msg
-            return True, ""
-        if "container" in tmpl:
-            c = tmpl["container"] or {}
-            cmd = list(c.get("command", []) or []) + list(c.get("args", []) or [])
-            if not cmd:
-                return False, "container template has no command"
-            ok, msg = await self._exec(cmd)
-            if ok:
-                self._collect_outputs(tmpl, outputs)
-            return ok, msg
-        if "script" in tmpl:
-            s = tmpl["script"] or {}
-            cmd = list(s.get("command", []) or ["sh"])
-            source = s.get("source", "")
-            ok, msg = await self._exec(cmd, stdin=source.encode())
-            if ok:
-                self._collect_outputs(tmpl, outputs)
-            return ok, msg
-        if "suspend" in tmpl:
-            dur = tmpl["suspend"] or {}
-            await asyncio.sleep(float(dur.get("duration", 0) or 0))
-            return True, ""
-        return False, "unsupported template type"
-
-    async def _exec(self, cmd: List[str], stdin: Optional[bytes] = None) -> Tuple[bool, str]:
+    @staticmethod
+    async def _bounded(run: Any, coro: Any, spec: Dict[str, Any],
+                       timeout_message: str) -> Tuple[Phase, str, bool]:
+        deadline = spec.get("activeDeadlineSeconds")
         try:
-            proc = await asyncio.create_subprocess_exec(
-                *[str(x) for x in cmd],
-                stdin=asyncio.subprocess.PIPE if stdin is not None else None,
-                stdout=asyncio.subprocess.PIPE,
-                stderr=asyncio.subprocess.PIPE,
-            )
-        except FileNotFoundError as e:
-            return False, str(e)
-        out, err = await proc.communicate(stdin)
-        if proc.returncode != 0:
-            tail = (err or out or b"").decode(errors="replace")[-500:]
-            return False, f"exit code {proc.returncode}: {tail}"
-        return True, ""
-
-    def _collect_outputs(self, tmpl: Dict[str, Any], outputs: List[Dict[str, Any]]) -> None:
-        for p in ((tmpl.get("outputs") or {}).get("parameters")) or []:
-            if not isinstance(p, dict):
-                continue
-            value = p.get("value")
-            if value is None and isinstance(p.get("valueFrom"), dict):
-                value = p["valueFrom"].get("default")
-            if value is None:
-                continue
-            outputs.append(
-                {
-                    "name": p.get("globalName") or p.get("name"),
-                    "value": value if isinstance(value, str) else json.dumps(value),
-                }
-            )
+            if deadline:
+                phase, message = await asyncio.wait_for(coro, float(deadline))
+            else:
+                phase, message = await coro
+            return phase, message, False
+        except asyncio.TimeoutError:
+            run.terminate(timeout_message)
+            return "Failed", timeout_message, True
+        except asyncio.CancelledError:
+            raise
+        except Exception as e:
+            coro.close()  # no-op unless it never started (bad deadline value)
+            run.terminate(str(e))
+            return "Failed", str(e), False

@@ -1,0 +1,527 @@
+"""One local run of an Argo-shaped workflow.
+
+:class:`WorkflowRun` walks the template tree of a validated spec, runs leaf
+templates as local subprocesses and records a node per step, Argo-style.
+:class:`~.engines.LocalWorkflowEngine` owns the Workflow object and its status
+writes; everything between the two writes happens here.
+"""
+from __future__ import annotations
+
+import asyncio
+import os
+import shutil
+import signal
+import tempfile
+import time
+from typing import Any, Awaitable, Dict, List, Optional, Tuple
+
+from .template import (
+    TemplateError,
+    UnresolvedReference,
+    eval_when,
+    item_display_name,
+    item_scope,
+    parse_duration,
+    parse_with_param,
+    substitute,
+    substitute_list,
+    to_str,
+)
+from .validate import task_dependencies
+
+#: ``outputs.result`` keeps at most this many bytes of a leaf's stdout
+RESULT_MAX_BYTES = 64 * 1024
+
+Scope = Dict[str, str]
+Outputs = Dict[str, Any]  # {"result": str, "parameters": {name: value}}
+#: (phase, message, outputs); outputs is None for skipped / fanned-out calls
+Result = Tuple[str, str, Optional[Outputs]]
+
+
+def _now_iso() -> str:
+    from ..api.types import k8s_now
+
+    return k8s_now()
+
+
+class WorkflowRun:
+    def __init__(self, spec: Dict[str, Any], name: str, namespace: str):
+        self.spec = spec
+        self.name = name
+        self.templates = {t.get("name"): t for t in spec.get("templates") or []}
+        self.nodes: Dict[str, Dict[str, Any]] = {}
+        self.global_outputs: List[Dict[str, str]] = []
+        self._procs: Dict[int, asyncio.subprocess.Process] = {}
+        self.base_scope: Scope = {"workflow.name": name, "workflow.namespace": namespace}
+        self.arguments: Dict[str, str] = {}
+        for p in (spec.get("arguments") or {}).get("parameters") or []:
+            if isinstance(p, dict) and p.get("name") is not None and p.get("value") is not None:
+                self.arguments[str(p["name"])] = to_str(p["value"])
+                self.base_scope[f"workflow.parameters.{p['name']}"] = to_str(p["value"])
+
+    # -- entry points -----------------------------------------------------
+
+    async def run_entrypoint(self) -> Tuple[str, str]:
+        return await self._run_root(self.spec.get("entrypoint"), self.name, self.base_scope)
+
+    async def run_exit_handler(self, status: str) -> Tuple[str, str]:
+        scope = dict(self.base_scope)
+        scope["workflow.status"] = status
+        return await self._run_root(self.spec["onExit"], f"{self.name}.onExit", scope)
+
+    async def _run_root(self, template: str, node_id: str, scope: Scope) -> Tuple[str, str]:
+        phase, message, _ = await self._run_template(
+            template, self.arguments, node_id, node_id, None, scope
+        )
+        return phase, message
+
+    def terminate(self, reason: str) -> None:
+        """After a cancellation: kill whatever is still alive and close the
+        nodes that were cut short."""
+        for proc in list(self._procs.values()):
+            _kill_group(proc)
+        now = _now_iso()
+        for node in self.nodes.values():
+            if "phase" not in node:
+                node.update(phase="Failed", message=reason, finishedAt=now)
+
+    # -- nodes ------------------------------------------------------------
+
+    def _open(self, node_id: str, display: str, type_: str, template: Optional[str],
+              parent: Optional[str]) -> Dict[str, Any]:
+        node: Dict[str, Any] = {
+            "id": node_id, "displayName": display, "type": type_,
+            "startedAt": _now_iso(), "children": [],
+        }
+        if template is not None:
+            node["templateName"] = template
+        self.nodes[node_id] = node
+        if parent is not None and parent in self.nodes:
+            self.nodes[parent]["children"].append(node_id)
+        return node
+
+    @staticmethod
+    def _close(node: Dict[str, Any], phase: str, message: str = "",
+               outputs: Optional[Outputs] = None) -> None:
+        node["phase"] = phase
+        node["message"] = message
+        node["finishedAt"] = _now_iso()
+        if outputs:
+            shown: Dict[str, Any] = {}
+            if outputs.get("result") is not None:
+                shown["result"] = outputs["result"]
+            if outputs.get("parameters"):
+                shown["parameters"] = [
+                    {"name": k, "value": v} for k, v in outputs["parameters"].items()
+                ]
+            if shown:
+                node["outputs"] = shown
+
+    def _mark(self, node_id: str, display: str, template: Optional[str], parent: Optional[str],
+              phase: str, message: str) -> None:
+        """A node that never ran: ``Skipped`` (false ``when``) or ``Omitted``."""
+        self._close(self._open(node_id, display, "Skipped", template, parent), phase, message)
+
+    # -- templates --------------------------------------------------------
+
+    def _inputs(self, tmpl: Dict[str, Any], args: Dict[str, str], scope: Scope) -> Scope:
+        """Template scope: workflow-level variables plus ``inputs.parameters``
+        (caller's argument, else ``value``, else ``default``)."""
+        out = {k: v for k, v in scope.items() if k.startswith("workflow.")}
+        for p in (tmpl.get("inputs") or {}).get("parameters") or []:
+            if not isinstance(p, dict) or p.get("name") is None:
+                continue
+            name = str(p["name"])
+            if name in args:
+                value = args[name]
+            elif p.get("value") is not None:
+                value = substitute(to_str(p["value"]), out)
+            elif p.get("default") is not None:
+                value = substitute(to_str(p["default"]), out)
+            else:
+                raise TemplateError(
+                    f"inputs.parameters.{name} was not supplied and has no default"
+                )
+            out[f"inputs.parameters.{name}"] = value
+        return out
+
+    async def _run_template(self, tname: Any, args: Dict[str, str], node_id: str, display: str,
+                            parent: Optional[str], wf_scope: Scope) -> Result:
+        tmpl = self.templates.get(tname) or {}
+        retry = tmpl.get("retryStrategy")
+        if not isinstance(retry, dict):
+            return await self._run_once(tmpl, args, node_id, display, parent, wf_scope, None)
+
+        node = self._open(node_id, display, "Retry", tname, parent)
+        try:
+            limit = int(str(substitute(retry.get("limit") or 0, wf_scope)).strip() or 0)
+            backoff = retry.get("backoff") if isinstance(retry.get("backoff"), dict) else None
+            wait = parse_duration(backoff.get("duration", 0)) if backoff else 0.0
+            factor = float(backoff.get("factor") or 1) if backoff else 1.0
+            max_duration = (
+                parse_duration(backoff["maxDuration"])
+                if backoff and backoff.get("maxDuration") is not None else None
+            )
+        except (TemplateError, ValueError) as e:
+            msg = f"invalid retryStrategy: {e}"
+            self._close(node, "Failed", msg)
+            return "Failed", msg, None
+        started = time.monotonic()
+        attempt = 0
+        while True:
+            phase, message, outputs = await self._run_once(
+                tmpl, args, f"{node_id}({attempt})", f"{display}({attempt})", node_id,
+                wf_scope, attempt,
+            )
+            if phase == "Succeeded" or attempt >= limit:
+                break
+            attempt += 1
+            delay = wait * factor ** (attempt - 1)
+            # a retry that would start later than maxDuration after the first
+            # attempt began never starts — so do not wait for it either
+            if max_duration is not None and time.monotonic() - started + delay > max_duration:
+                break
+            if delay > 0:
+                await asyncio.sleep(delay)
+        self._close(node, phase, message, outputs)
+        return phase, message, outputs
+
+    async def _run_once(self, tmpl: Dict[str, Any], args: Dict[str, str], node_id: str,
+                        display: str, parent: Optional[str], wf_scope: Scope,
+                        attempt: Optional[int]) -> Result:
+        tname = tmpl.get("name")
+        if "steps" in tmpl:
+            type_ = "Steps"
+        elif "dag" in tmpl:
+            type_ = "DAG"
+        elif "suspend" in tmpl:
+            type_ = "Suspend"
+        else:
+            type_ = "Pod"
+        node = self._open(node_id, display, type_, tname, parent)
+        outputs: Optional[Outputs] = None
+        try:
+            scope = self._inputs(tmpl, args, wf_scope)
+            if attempt is not None:
+                scope["retries"] = str(attempt)
+            if type_ == "Steps":
+                ok, message = await self._run_steps(tmpl, node_id, scope)
+            elif type_ == "DAG":
+                ok, message = await self._run_dag(tmpl, node_id, scope)
+            elif type_ == "Suspend":
+                duration = substitute((tmpl["suspend"] or {}).get("duration", 0) or 0, scope)
+                await asyncio.sleep(parse_duration(duration))
+                ok, message = True, ""
+            elif "container" in tmpl or "script" in tmpl:
+                ok, message, outputs = await self._run_leaf(tmpl, scope)
+            else:
+                ok, message = False, "unsupported template type"
+            if ok and type_ in ("Steps", "DAG"):
+                outputs = self._composite_outputs(tmpl, scope)
+        except TemplateError as e:
+            ok, message, outputs = False, str(e), None
+        if ok and outputs:
+            self._export_globals(tmpl, outputs, leaf=type_ == "Pod")
+        phase = "Succeeded" if ok else "Failed"
+        self._close(node, phase, message, outputs)
+        return phase, message, outputs if ok else None
+
+    def _export_globals(self, tmpl: Dict[str, Any], outputs: Outputs, leaf: bool) -> None:
+        """Surface output parameters into ``status.outputs.parameters`` (the
+        custom-metrics contract). Leaf parameters surface under ``globalName``
+        or, lacking one, their own name; composite templates only re-export
+        what carries a ``globalName``."""
+        for p in (tmpl.get("outputs") or {}).get("parameters") or []:
+            if not isinstance(p, dict) or p.get("name") not in outputs["parameters"]:
+                continue
+            if leaf or p.get("globalName"):
+                self.global_outputs.append({
+                    "name": p.get("globalName") or p["name"],
+                    "value": outputs["parameters"][p["name"]],
+                })
+
+    def _composite_outputs(self, tmpl: Dict[str, Any], scope: Scope) -> Optional[Outputs]:
+        params: Dict[str, str] = {}
+        for p in (tmpl.get("outputs") or {}).get("parameters") or []:
+            if not isinstance(p, dict) or p.get("name") is None:
+                continue
+            value_from = p.get("valueFrom") if isinstance(p.get("valueFrom"), dict) else {}
+            if p.get("value") is not None:
+                params[p["name"]] = substitute(to_str(p["value"]), scope)
+            elif value_from.get("parameter") is not None:
+                try:
+                    params[p["name"]] = substitute(to_str(value_from["parameter"]), scope)
+                except UnresolvedReference:
+                    if value_from.get("default") is None:
+                        raise
+                    params[p["name"]] = to_str(value_from["default"])
+            elif value_from.get("default") is not None:
+                params[p["name"]] = to_str(value_from["default"])
+        return {"result": None, "parameters": params} if params else None
+
+    # -- steps and DAGs ---------------------------------------------------
+
+    async def _run_steps(self, tmpl: Dict[str, Any], node_id: str, scope: Scope) -> Tuple[bool, str]:
+        for i, group in enumerate(tmpl["steps"] or []):
+            steps = [s for s in (group if isinstance(group, list) else [group])
+                     if isinstance(s, dict)]
+            gid = f"{node_id}[{i}]"
+            gnode = self._open(gid, f"[{i}]", "StepGroup", None, node_id)
+            results = await _gather(
+                [self._run_call(s, "steps", gid, f"{gid}.{s.get('name')}", scope) for s in steps]
+            )
+            failed = [msg for phase, msg, _ in results if phase == "Failed"]
+            self._close(gnode, "Failed" if failed else "Succeeded", failed[0] if failed else "")
+            if failed:
+                return False, failed[0]
+        return True, ""
+
+    async def _run_dag(self, tmpl: Dict[str, Any], node_id: str, scope: Scope) -> Tuple[bool, str]:
+        dag = tmpl["dag"] or {}
+        tasks = {t.get("name"): t for t in dag.get("tasks") or [] if isinstance(t, dict)}
+        deps = {name: task_dependencies(t) for name, t in tasks.items()}
+        fail_fast = dag.get("failFast", True) is not False
+        phases: Dict[str, str] = {}
+        running: Dict["asyncio.Future[Result]", str] = {}
+        first_failure: Optional[str] = None
+
+        def omit(name: str, why: str) -> None:
+            phases[name] = "Omitted"
+            self._mark(f"{node_id}.{name}", name, tasks[name].get("template"), node_id,
+                       "Omitted", why)
+
+        try:
+            while True:
+                for name in tasks:
+                    if name in phases or name in running.values():
+                        continue
+                    if first_failure is not None and fail_fast:
+                        continue
+                    states = [phases.get(d) for d in deps[name]]
+                    if any(s in ("Failed", "Omitted") for s in states):
+                        omit(name, "omitted: a dependency did not succeed")
+                    elif all(s in ("Succeeded", "Skipped") for s in states):
+                        fut = asyncio.ensure_future(self._run_call(
+                            tasks[name], "tasks", node_id, f"{node_id}.{name}", scope
+                        ))
+                        running[fut] = name
+                if not running:
+                    break
+                done, _ = await asyncio.wait(running, return_when=asyncio.FIRST_COMPLETED)
+                for fut in sorted(done, key=lambda f: list(running).index(f)):
+                    name = running.pop(fut)
+                    phase, message, _ = fut.result()
+                    phases[name] = phase
+                    if phase == "Failed" and first_failure is None:
+                        first_failure = message
+        finally:
+            await _cancel_all(list(running))
+        for name in tasks:
+            if name not in phases:
+                omit(name, "omitted: the DAG failed before this task could start")
+        if first_failure is not None:
+            return False, first_failure
+        return True, ""
+
+    async def _run_call(self, call: Dict[str, Any], kind: str, parent: str, node_id: str,
+                        scope: Scope) -> Result:
+        """One step or DAG task: loop expansion, ``when``, arguments, then
+        the template it names. Publishes ``steps.NAME.*`` / ``tasks.NAME.*``
+        into the caller's scope when it ran exactly once."""
+        name = str(call.get("name"))
+        tname = call.get("template")
+        try:
+            if "withItems" in call or "withParam" in call:
+                if "withItems" in call:
+                    items = call["withItems"]
+                    if not isinstance(items, list):
+                        raise TemplateError("withItems is not a list")
+                else:
+                    items = parse_with_param(substitute(to_str(call["withParam"]), scope))
+                results = await _gather([
+                    self._run_expanded(
+                        call, parent, f"{parent}.{item_display_name(name, i, item)}",
+                        item_display_name(name, i, item), {**scope, **item_scope(item)},
+                    )
+                    for i, item in enumerate(items)
+                ])
+                failed = [msg for phase, msg, _ in results if phase == "Failed"]
+                scope[f"{kind}.{name}.status"] = "Failed" if failed else "Succeeded"
+                return ("Failed", failed[0], None) if failed else ("Succeeded", "", None)
+            phase, message, outputs = await self._run_expanded(call, parent, node_id, name, scope)
+        except TemplateError as e:
+            self._mark(node_id, name, tname, parent, "Failed", str(e))
+            return "Failed", str(e), None
+        scope[f"{kind}.{name}.status"] = phase
+        if phase == "Succeeded" and outputs:
+            if outputs.get("result") is not None:
+                scope[f"{kind}.{name}.outputs.result"] = outputs["result"]
+            for k, v in (outputs.get("parameters") or {}).items():
+                scope[f"{kind}.{name}.outputs.parameters.{k}"] = v
+        return phase, message, outputs
+
+    async def _run_expanded(self, call: Dict[str, Any], parent: str, node_id: str, display: str,
+                            scope: Scope) -> Result:
+        tname = call.get("template")
+        try:
+            if call.get("when") is not None:
+                expr = substitute(to_str(call["when"]), scope)
+                if not eval_when(expr):
+                    message = f"when {expr!r} evaluated false"
+                    self._mark(node_id, display, tname, parent, "Skipped", message)
+                    return "Skipped", message, None
+            args: Dict[str, str] = {}
+            for p in (call.get("arguments") or {}).get("parameters") or []:
+                if isinstance(p, dict) and p.get("name") is not None and p.get("value") is not None:
+                    args[str(p["name"])] = substitute(to_str(p["value"]), scope)
+        except TemplateError as e:
+            self._mark(node_id, display, tname, parent, "Failed", str(e))
+            return "Failed", str(e), None
+        return await self._run_template(tname, args, node_id, display, parent, scope)
+
+    # -- leaves -----------------------------------------------------------
+
+    async def _run_leaf(self, tmpl: Dict[str, Any], scope: Scope) -> Tuple[bool, str, Optional[Outputs]]:
+        stdin: Optional[bytes] = None
+        if "container" in tmpl:
+            body = tmpl["container"] or {}
+            cmd = substitute_list(body.get("command"), scope) + substitute_list(
+                body.get("args"), scope
+            )
+            if not cmd:
+                return False, "container template has no command", None
+        else:
+            body = tmpl["script"] or {}
+            cmd = substitute_list(body.get("command"), scope) or ["sh"]
+            stdin = str(substitute(body.get("source", "") or "", scope)).encode()
+        env = None
+        for e in body.get("env") or []:
+            # valueFrom sources (secrets, field refs) have no local equivalent
+            if isinstance(e, dict) and e.get("name") is not None and e.get("value") is not None:
+                if env is None:
+                    env = dict(os.environ)
+                env[str(e["name"])] = str(substitute(to_str(e["value"]), scope))
+
+        out_params = [
+            p for p in (tmpl.get("outputs") or {}).get("parameters") or []
+            if isinstance(p, dict) and p.get("name") is not None
+        ]
+        needs_dir = any(
+            isinstance(p.get("valueFrom"), dict) and p["valueFrom"].get("path") is not None
+            for p in out_params
+        )
+        workdir = tempfile.mkdtemp(prefix="am-wf-") if needs_dir else None
+        try:
+            ok, message, stdout = await self._exec(cmd, stdin, env, workdir)
+            if not ok:
+                return False, message, None
+            params: Dict[str, str] = {}
+            for p in out_params:
+                value_from = p.get("valueFrom") if isinstance(p.get("valueFrom"), dict) else {}
+                value: Any = None
+                if p.get("value") is not None:
+                    value = substitute(to_str(p["value"]), scope)
+                elif value_from.get("path") is not None:
+                    path = os.path.join(workdir or "", str(substitute(value_from["path"], scope)))
+                    try:
+                        with open(path, "rb") as f:
+                            value = f.read(RESULT_MAX_BYTES).decode(errors="replace")
+                        if value.endswith("\n"):
+                            value = value[:-1]
+                    except OSError:
+                        if value_from.get("default") is None:
+                            return False, (
+                                f"output parameter {p['name']!r}: "
+                                f"{value_from['path']} not found and no default given"
+                            ), None
+                        value = to_str(value_from["default"])
+                elif value_from.get("default") is not None:
+                    value = to_str(value_from["default"])
+                if value is not None:
+                    params[str(p["name"])] = value
+            result = stdout[:RESULT_MAX_BYTES].decode(errors="replace")
+            if result.endswith("\n"):
+                result = result[:-1]
+            return True, "", {"result": result, "parameters": params}
+        finally:
+            if workdir is not None:
+                shutil.rmtree(workdir, ignore_errors=True)
+
+    async def _exec(self, cmd: List[str], stdin: Optional[bytes], env: Optional[Dict[str, str]],
+                    cwd: Optional[str]) -> Tuple[bool, str, bytes]:
+        """Run one process in a session of its own, so that the whole group
+        — shells and whatever they started — can be killed on cancellation."""
+        spawn = asyncio.ensure_future(asyncio.create_subprocess_exec(
+            *cmd,
+            stdin=asyncio.subprocess.PIPE if stdin is not None else None,
+            stdout=asyncio.subprocess.PIPE,
+            stderr=asyncio.subprocess.PIPE,
+            env=env, cwd=cwd, start_new_session=True,
+        ))
+        try:
+            proc = await asyncio.shield(spawn)
+        except asyncio.CancelledError:
+            # cancelled in the middle of the spawn: let it finish, so that
+            # the child is known and can be killed like any other
+            try:
+                late = await spawn
+            except BaseException:
+                late = None
+            if late is not None:
+                _kill_group(late)
+                await late.wait()
+            raise
+        except (OSError, ValueError) as e:
+            return False, str(e), b""
+        self._procs[proc.pid] = proc
+        try:
+            out, err = await proc.communicate(stdin)
+        except BaseException:
+            _kill_group(proc)
+            try:
+                await proc.wait()
+            except asyncio.CancelledError:
+                pass
+            raise
+        finally:
+            self._procs.pop(proc.pid, None)
+        if proc.returncode != 0:
+            tail = (err or out or b"").decode(errors="replace")[-500:]
+            return False, f"exit code {proc.returncode}: {tail}", out
+        return True, "", out
+
+
+def _kill_group(proc: "asyncio.subprocess.Process") -> None:
+    """SIGKILL the process group led by ``proc``.
+
+    The leader may already have exited and been reaped — a shell that put a
+    child in the background and returned — while that child keeps the
+    leaf's stdout open and so keeps the leaf "running"; the group is
+    signalled all the same. This is only called for a leaf whose pipes are
+    still open, i.e. while some member of the group is still there, and as
+    long as one is, the kernel cannot hand the group id to anyone else. An
+    empty group is ESRCH, which is ignored."""
+    try:
+        os.killpg(proc.pid, signal.SIGKILL)
+    except (ProcessLookupError, PermissionError):
+        pass
+
+
+async def _cancel_all(tasks: List["asyncio.Future[Any]"]) -> None:
+    for t in tasks:
+        t.cancel()
+    if tasks:
+        await asyncio.gather(*tasks, return_exceptions=True)
+
+
+async def _gather(coros: List[Awaitable[Result]]) -> List[Result]:
+    """Run ``coros`` concurrently and return their results in order. If the
+    caller is cancelled, every child is cancelled and awaited first, so no
+    subprocess outlives its workflow."""
+    tasks = [asyncio.ensure_future(c) for c in coros]
+    try:
+        if tasks:
+            await asyncio.wait(tasks)
+    finally:
+        await _cancel_all([t for t in tasks if not t.done()])
+    return [t.result() for t in tasks]

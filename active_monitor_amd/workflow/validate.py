@@ -1,0 +1,232 @@
+"""Static checks for the workflow surface the local executor runs.
+
+:func:`validate_workflow_spec` returns human-readable problems, in a stable
+order, without starting anything. The engine calls it before the first
+process and fails the workflow with the first problem; the ``lint`` command
+prints all of them.
+"""
+from __future__ import annotations
+
+import re
+from typing import Any, Dict, List, Optional, Set
+
+from .template import find_refs, find_strings
+
+#: template body types the local executor runs
+BODY_TYPES = ("container", "script", "steps", "dag", "suspend")
+#: body types Argo knows that have no local equivalent
+UNSUPPORTED_BODY_TYPES = ("resource", "http", "data", "containerSet", "plugin")
+
+_WORKFLOW_VARS = {"workflow.name", "workflow.namespace", "workflow.status"}
+_DEPENDS_RE = re.compile(r"^[A-Za-z0-9_\-]+(\s*&&\s*[A-Za-z0-9_\-]+)*$")
+
+
+def parse_depends(expr: Any) -> Optional[List[str]]:
+    """Task names of a ``depends`` that is only bare names joined by ``&&``;
+    None for anything else (``A.Failed``, ``||``, ``!``, parentheses)."""
+    if not isinstance(expr, str) or not _DEPENDS_RE.match(expr.strip()):
+        return None
+    return [p.strip() for p in expr.split("&&")]
+
+
+def task_dependencies(task: Dict[str, Any]) -> List[str]:
+    """Dependencies of one DAG task (``dependencies`` list and/or a
+    supported ``depends``), duplicates removed, order kept."""
+    deps: List[str] = []
+    raw = task.get("dependencies")
+    if isinstance(raw, list):
+        deps.extend(str(d) for d in raw)
+    if task.get("depends"):
+        deps.extend(parse_depends(task["depends"]) or [])
+    return list(dict.fromkeys(deps))
+
+
+def _param_names(params: Any) -> Set[str]:
+    return {
+        str(p["name"]) for p in (params or []) if isinstance(p, dict) and p.get("name") is not None
+    }
+
+
+def _calls(tmpl: Dict[str, Any]) -> List[Dict[str, Any]]:
+    """The steps or DAG tasks of a composite template, flattened."""
+    if "steps" in tmpl:
+        out = []
+        for group in tmpl.get("steps") or []:
+            for s in group if isinstance(group, list) else [group]:
+                if isinstance(s, dict):
+                    out.append(s)
+        return out
+    if "dag" in tmpl:
+        return [t for t in ((tmpl.get("dag") or {}).get("tasks") or []) if isinstance(t, dict)]
+    return []
+
+
+def _find_cycle(deps: Dict[str, List[str]]) -> Optional[str]:
+    """Name of a task that sits on a dependency cycle, or None."""
+    WHITE, GREY, BLACK = 0, 1, 2
+    color = {n: WHITE for n in deps}
+    for root in deps:
+        if color[root] != WHITE:
+            continue
+        stack = [(root, iter(deps[root]))]
+        color[root] = GREY
+        while stack:
+            node, it = stack[-1]
+            for nxt in it:
+                if nxt not in color:
+                    continue
+                if color[nxt] == GREY:
+                    return nxt
+                if color[nxt] == WHITE:
+                    color[nxt] = GREY
+                    stack.append((nxt, iter(deps[nxt])))
+                    break
+            else:
+                color[node] = BLACK
+                stack.pop()
+    return None
+
+
+def _check_refs(where: str, obj: Any, inputs: Set[str], wf_params: Set[str],
+                call_names: Set[str], kind: str, problems: List[str],
+                in_loop: bool = False) -> None:
+    """``in_loop``: ``obj`` is a step or task that carries ``withItems`` /
+    ``withParam`` — the only place where ``{{item}}`` means anything."""
+    for text in find_strings(obj):
+        if "{{=" in text.replace(" ", ""):
+            problems.append(f"{where}: expression tags ({{{{=...}}}}) are not supported")
+            break
+    for ref in dict.fromkeys(find_refs(obj)):
+        head, _, rest = ref.partition(".")
+        if head == "inputs":
+            if not rest.startswith("parameters."):
+                problems.append(f"{where}: unsupported reference {{{{{ref}}}}}")
+            elif rest[len("parameters."):] not in inputs:
+                problems.append(
+                    f"{where}: {{{{{ref}}}}} refers to an undeclared input parameter"
+                )
+        elif head == "workflow":
+            if rest.startswith("parameters."):
+                if rest[len("parameters."):] not in wf_params:
+                    problems.append(
+                        f"{where}: {{{{{ref}}}}} refers to an undeclared workflow parameter"
+                    )
+            elif ref not in _WORKFLOW_VARS:
+                problems.append(f"{where}: unsupported reference {{{{{ref}}}}}")
+        elif head in ("steps", "tasks"):
+            if head != kind:
+                problems.append(
+                    f"{where}: {{{{{ref}}}}} is not available in this template"
+                )
+            # task names may contain dots only in theory; match the longest
+            elif not any(rest == n or rest.startswith(n + ".") for n in call_names):
+                problems.append(f"{where}: {{{{{ref}}}}} refers to an unknown {head[:-1]}")
+        elif head == "item":
+            if not in_loop:
+                problems.append(
+                    f"{where}: {{{{{ref}}}}} is only available in a step or task "
+                    "with withItems or withParam"
+                )
+        elif head == "retries":
+            if rest:
+                problems.append(f"{where}: unsupported reference {{{{{ref}}}}}")
+        else:
+            problems.append(f"{where}: unknown variable namespace in {{{{{ref}}}}}")
+
+
+def validate_workflow_spec(spec: Any) -> List[str]:
+    """Problems that would stop ``spec`` from running locally; ``[]`` when
+    it is clean."""
+    if not isinstance(spec, dict):
+        return ["workflow spec is not a map"]
+    problems: List[str] = []
+    templates: Dict[str, Dict[str, Any]] = {}
+    for t in spec.get("templates") or []:
+        if not isinstance(t, dict) or t.get("name") is None:
+            problems.append("a template has no name")
+            continue
+        if t["name"] in templates:
+            problems.append(f"template {t['name']!r} is defined more than once")
+        templates[t["name"]] = t
+
+    entry = spec.get("entrypoint")
+    if entry not in templates:
+        problems.append(f"entrypoint {entry!r} not found")
+    on_exit = spec.get("onExit")
+    if on_exit is not None and on_exit not in templates:
+        problems.append(f"onExit template {on_exit!r} not found")
+
+    wf_params = _param_names((spec.get("arguments") or {}).get("parameters"))
+    _check_refs("spec.arguments", spec.get("arguments"), set(), wf_params, set(), "", problems)
+
+    for name, tmpl in templates.items():
+        where = f"template {name!r}"
+        if "templateRef" in tmpl:
+            problems.append(f"{where}: templateRef is not supported")
+        bodies = [b for b in BODY_TYPES if b in tmpl]
+        foreign = [b for b in UNSUPPORTED_BODY_TYPES if b in tmpl]
+        if foreign:
+            problems.append(f"{where}: {foreign[0]} templates are not supported")
+        elif not bodies:
+            problems.append(
+                f"{where}: no body (expected one of {', '.join(BODY_TYPES)})"
+            )
+        if len(bodies) + len(foreign) > 1:
+            problems.append(
+                f"{where}: several bodies ({', '.join(bodies + foreign)}); expected exactly one"
+            )
+
+        calls = _calls(tmpl)
+        kind = "tasks" if "dag" in tmpl else ("steps" if "steps" in tmpl else "")
+        seen: Set[str] = set()
+        for call in calls:
+            cname = call.get("name")
+            cwhere = f"{where}: {kind[:-1]} {cname!r}"
+            if cname is None:
+                problems.append(f"{where}: a {kind[:-1]} has no name")
+            elif cname in seen:
+                problems.append(f"{cwhere} is defined more than once")
+            seen.add(cname)
+            if "templateRef" in call:
+                problems.append(f"{cwhere}: templateRef is not supported")
+            elif call.get("template") not in templates:
+                problems.append(f"{cwhere}: template {call.get('template')!r} not found")
+            for key in ("withSequence", "continueOn"):
+                if key in call:
+                    problems.append(f"{cwhere}: {key} is not supported")
+            if "withItems" in call and "withParam" in call:
+                problems.append(f"{cwhere}: withItems and withParam are mutually exclusive")
+            if "withItems" in call and not isinstance(call["withItems"], list):
+                problems.append(f"{cwhere}: withItems is not a list")
+
+        if kind == "tasks":
+            deps: Dict[str, List[str]] = {}
+            for task in calls:
+                tname = task.get("name")
+                twhere = f"{where}: task {tname!r}"
+                if task.get("depends") and parse_depends(task["depends"]) is None:
+                    problems.append(
+                        f"{twhere}: unsupported depends expression {task['depends']!r} "
+                        "(only task names joined by && are supported)"
+                    )
+                if "dependencies" in task and not isinstance(task["dependencies"], list):
+                    problems.append(f"{twhere}: dependencies is not a list")
+                deps[tname] = task_dependencies(task)
+                for d in deps[tname]:
+                    if d not in seen:
+                        problems.append(f"{twhere}: depends on unknown task {d!r}")
+            cyc = _find_cycle(deps)
+            if cyc is not None:
+                problems.append(f"{where}: dependency cycle through task {cyc!r}")
+
+        inputs = _param_names((tmpl.get("inputs") or {}).get("parameters"))
+        names = {str(n) for n in seen if n is not None}
+        # the template's own fields first, then each step or task on its own:
+        # {{item}} is valid only inside one that loops
+        body = {k: v for k, v in tmpl.items() if k not in ("steps", "dag")}
+        _check_refs(where, body, inputs, wf_params, names, kind, problems)
+        for call in calls:
+            _check_refs(f"{where}: {kind[:-1]} {call.get('name')!r}", call, inputs, wf_params,
+                        names, kind, problems,
+                        in_loop="withItems" in call or "withParam" in call)
+    return problems
