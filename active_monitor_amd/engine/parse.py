@@ -61,7 +61,7 @@ _PARSE_CACHE: Dict[bytes, Dict[str, Any]] = {}
 _PARSE_CACHE_MAX = 2048
 
 
-def _decode(content: bytes, remedy: bool) -> Dict[str, Any]:
+def _decode(content: bytes) -> Dict[str, Any]:
     from ..utils.fastcopy import deep_copy
 
     cached = _PARSE_CACHE.get(content)
@@ -126,86 +126,81 @@ async def _read_source_async(resource) -> bytes:
         ) from None
 
 
-def parse_workflow_from_healthcheck(
-    hc: HealthCheck, content: Optional[bytes] = None
+def parse_from_healthcheck(
+    hc: HealthCheck, remedy: bool, content: Optional[bytes] = None
 ) -> Tuple[Dict[str, Any], Dict[str, str]]:
-    """Returns ``(spec_dict, labels)`` for the health-check workflow, mutating
-    ``hc.spec.workflow.timeout`` when it defaults from RepeatAfterSec
-    (reference :980-995). ``content`` short-circuits the artifact read (used
-    by the async variant, which offloads blocking sources to a thread)."""
+    """Returns ``(spec_dict, labels)`` for the health-check workflow or, with
+    ``remedy``, the remedy workflow. The two differ only in the error strings
+    and in the deadline rule at the end. ``content`` short-circuits the
+    artifact read (used by the async variant, which offloads blocking sources
+    to a thread)."""
+    wf = hc.spec.remedy_workflow if remedy else hc.spec.workflow
     if content is None:
         content = b""
-        if hc.spec.workflow.resource is not None:
-            reader = get_artifact_reader(hc.spec.workflow.resource.source)
-            content = reader.read()
-    data = _decode(content, remedy=False)
+        if wf.resource is not None:
+            content = get_artifact_reader(wf.resource.source).read()
+    data = _decode(content)
     labels = _extract_labels(data)
-    spec = _validated_spec(data, remedy=False)
+    spec = _validated_spec(data, remedy)
 
     if spec.get("podGC") is None:
         spec["podGC"] = {"strategy": POD_GC_ON_POD_COMPLETION}
+    if wf.resource is not None and wf.resource.service_account:
+        spec["serviceAccountName"] = wf.resource.service_account
 
-    if hc.spec.workflow.timeout == 0:
-        hc.spec.workflow.timeout = hc.spec.repeat_after_sec
-    timeout = hc.spec.workflow.timeout
-
-    if hc.spec.workflow.resource is not None and hc.spec.workflow.resource.service_account:
-        spec["serviceAccountName"] = hc.spec.workflow.resource.service_account
-
-    if spec.get("activeDeadlineSeconds") is None:
-        spec["activeDeadlineSeconds"] = timeout
+    deadline = spec.get("activeDeadlineSeconds")
+    if not remedy:
+        # Workflow.Timeout defaults from RepeatAfterSec — a spec mutation that
+        # later feeds the backoff computation (reference :980-995)
+        if wf.timeout == 0:
+            wf.timeout = hc.spec.repeat_after_sec
+        if deadline is None:
+            spec["activeDeadlineSeconds"] = wf.timeout
+    else:
+        # the deadline defaults from RepeatAfterSec; an existing numeric one
+        # round-trips into RemedyWorkflow.Timeout (reference :1108-1120)
+        timeout = hc.spec.repeat_after_sec
+        if deadline is None:
+            spec["activeDeadlineSeconds"] = timeout
+        elif isinstance(deadline, (int, float)) and not isinstance(deadline, bool):
+            timeout = int(deadline)
+        wf.timeout = timeout
     return spec, labels
 
 
-async def parse_workflow_from_healthcheck_async(
-    hc: HealthCheck,
+async def parse_from_healthcheck_async(
+    hc: HealthCheck, remedy: bool
 ) -> Tuple[Dict[str, Any], Dict[str, str]]:
     """Event-loop-safe variant: blocking sources (URL/file) are read on a
     worker thread with a timeout before the pure-CPU parse runs on-loop."""
-    content = await _read_source_async(hc.spec.workflow.resource)
-    return parse_workflow_from_healthcheck(hc, content=content)
+    wf = hc.spec.remedy_workflow if remedy else hc.spec.workflow
+    content = await _read_source_async(wf.resource)
+    return parse_from_healthcheck(hc, remedy, content)
+
+
+def parse_workflow_from_healthcheck(
+    hc: HealthCheck, content: Optional[bytes] = None
+) -> Tuple[Dict[str, Any], Dict[str, str]]:
+    """Health-check workflow (reference :876-1000); mutates
+    ``hc.spec.workflow.timeout`` when it defaults from RepeatAfterSec."""
+    return parse_from_healthcheck(hc, False, content)
 
 
 def parse_remedy_workflow_from_healthcheck(
     hc: HealthCheck, content: Optional[bytes] = None
 ) -> Tuple[Dict[str, Any], Dict[str, str]]:
-    """Remedy variant (reference :1002-1125): ``activeDeadlineSeconds``
-    defaults from RepeatAfterSec; an existing numeric deadline round-trips
-    into ``hc.spec.remedy_workflow.timeout``."""
-    if content is None:
-        content = b""
-        if hc.spec.remedy_workflow.resource is not None:
-            reader = get_artifact_reader(hc.spec.remedy_workflow.resource.source)
-            content = reader.read()
-    data = _decode(content, remedy=True)
-    labels = _extract_labels(data)
-    spec = _validated_spec(data, remedy=True)
+    """Remedy workflow (reference :1002-1125); sets
+    ``hc.spec.remedy_workflow.timeout``."""
+    return parse_from_healthcheck(hc, True, content)
 
-    if spec.get("podGC") is None:
-        spec["podGC"] = {"strategy": POD_GC_ON_POD_COMPLETION}
 
-    if (
-        hc.spec.remedy_workflow.resource is not None
-        and hc.spec.remedy_workflow.resource.service_account
-    ):
-        spec["serviceAccountName"] = hc.spec.remedy_workflow.resource.service_account
-
-    timeout = hc.spec.repeat_after_sec
-    deadline = spec.get("activeDeadlineSeconds")
-    if deadline is None:
-        spec["activeDeadlineSeconds"] = timeout
-        hc.spec.remedy_workflow.timeout = timeout
-    elif isinstance(deadline, (int, float)) and not isinstance(deadline, bool):
-        hc.spec.remedy_workflow.timeout = int(deadline)
-    else:
-        hc.spec.remedy_workflow.timeout = timeout
-    return spec, labels
+async def parse_workflow_from_healthcheck_async(
+    hc: HealthCheck,
+) -> Tuple[Dict[str, Any], Dict[str, str]]:
+    return await parse_from_healthcheck_async(hc, False)
 
 
 async def parse_remedy_workflow_from_healthcheck_async(
     hc: HealthCheck,
 ) -> Tuple[Dict[str, Any], Dict[str, str]]:
-    """Event-loop-safe remedy variant (see
-    :func:`parse_workflow_from_healthcheck_async`)."""
-    content = await _read_source_async(hc.spec.remedy_workflow.resource)
-    return parse_remedy_workflow_from_healthcheck(hc, content=content)
+    return await parse_from_healthcheck_async(hc, True)

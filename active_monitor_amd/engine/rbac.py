@@ -16,7 +16,9 @@ Re-implements the reference's SA/Role/ClusterRole/Binding lifecycle
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional
+import os
+import time
+from typing import Any, Callable, Dict, List, Optional
 
 from ..api.types import HealthCheck, PolicyRule
 from ..kube.client import EventRecorder, KubeClient
@@ -29,6 +31,13 @@ WF_MANAGED_BY_VALUE = "active-monitor"
 
 CLUSTER_LEVEL = "cluster"
 NAMESPACE_LEVEL = "namespace"
+
+# spec.level → (role kind, suffix of the role name derived from the SA); the
+# binding is "<role kind>Binding" named "<role name>-binding" (:306-309,321-324)
+_ROLE_BY_LEVEL = {
+    CLUSTER_LEVEL: ("ClusterRole", "-cluster-role"),
+    NAMESPACE_LEVEL: ("Role", "-ns-role"),
+}
 
 # Least-privilege read-only rules for monitoring workflows
 # (healthcheck_controller.go:85-101).
@@ -99,8 +108,6 @@ class RBACProvisioner:
 
     def __init__(self, client: KubeClient, recorder: Optional[EventRecorder] = None,
                  ensure_ttl: Optional[float] = None):
-        import os
-
         self.client = client
         self.recorder = recorder
         if ensure_ttl is None:
@@ -110,183 +117,54 @@ class RBACProvisioner:
         self._ensured: Dict[tuple, float] = {}
 
     def _fresh(self, key: tuple) -> bool:
-        import time
-
         if self.ensure_ttl <= 0:
             return False
         exp = self._ensured.get(key)
         return exp is not None and exp > time.monotonic()
 
     def _mark(self, key: tuple) -> None:
-        import time
-
         if self.ensure_ttl > 0:
             if len(self._ensured) > 50000:
                 now = time.monotonic()
                 self._ensured = {k: v for k, v in self._ensured.items() if v > now}
             self._ensured[key] = time.monotonic() + self.ensure_ttl
 
-    def _invalidate(self, kind: str, namespace: str, name: str) -> None:
-        self._ensured.pop((kind, namespace, name), None)
-
     async def _event(self, hc_obj: Dict[str, Any], ev_type: str, message: str) -> None:
         if self.recorder is not None:
             await self.recorder.event(hc_obj, ev_type, ev_type, message)
 
-    # -- creates (get-then-create, reuse if present) -----------------------
-
-    async def create_service_account(self, name: str, namespace: str) -> str:
-        cache_key = ("ServiceAccount", namespace, name)
+    async def _ensure(
+        self, api_version: str, kind: str, namespace: str, name: str,
+        body_fn: Optional[Callable[[], Dict[str, Any]]] = None,
+    ) -> None:
+        """Get-then-create, reusing the object if present. ``namespace`` is ""
+        for cluster-scoped kinds; ``body_fn`` builds the fields beyond
+        metadata and runs only when the object has to be created."""
+        cache_key = (kind, namespace, name)
         if self._fresh(cache_key):
-            return name
+            return
         try:
-            sa = await self.client.get("v1", "ServiceAccount", namespace, name)
-            self._mark(cache_key)
-            return sa["metadata"]["name"]
+            await self.client.get(api_version, kind, namespace, name)
         except NotFoundError:
-            pass
-        sa = {
-            "apiVersion": "v1",
-            "kind": "ServiceAccount",
-            "metadata": {"name": name, "namespace": namespace, "labels": _managed_labels()},
-        }
-        try:
-            created = await self.client.create(sa, transfer=True)
-        except AlreadyExistsError:
-            # concurrent reconciles sharing an SA race get-then-create;
-            # losing the race means the object exists — reuse it
-            self._mark(cache_key)
-            return name
+            metadata: Dict[str, Any] = {"name": name}
+            if namespace:
+                metadata["namespace"] = namespace
+            metadata["labels"] = _managed_labels()
+            obj = {"apiVersion": api_version, "kind": kind, "metadata": metadata}
+            if body_fn is not None:
+                obj.update(body_fn())
+            try:
+                await self.client.create(obj, transfer=True)
+            except AlreadyExistsError:
+                # concurrent reconciles sharing an SA race get-then-create;
+                # losing the race means the object exists — reuse it
+                pass
         self._mark(cache_key)
-        return created["metadata"]["name"]
-
-    async def create_cluster_role(self, name: str, rules: List[PolicyRule]) -> str:
-        cache_key = ("ClusterRole", "", name)
-        if self._fresh(cache_key):
-            return name
-        try:
-            cr = await self.client.get(RBAC_API_VERSION, "ClusterRole", "", name)
-            self._mark(cache_key)
-            return cr["metadata"]["name"]
-        except NotFoundError:
-            pass
-        cr = {
-            "apiVersion": RBAC_API_VERSION,
-            "kind": "ClusterRole",
-            "metadata": {"name": name, "labels": _managed_labels()},
-            "rules": [r.to_dict() for r in rules],
-        }
-        try:
-            created = await self.client.create(cr, transfer=True)
-        except AlreadyExistsError:
-            # concurrent reconciles sharing an SA race get-then-create;
-            # losing the race means the object exists — reuse it
-            self._mark(cache_key)
-            return name
-        self._mark(cache_key)
-        return created["metadata"]["name"]
-
-    async def create_cluster_role_binding(
-        self, name: str, role_name: str, sa_name: str, sa_namespace: str
-    ) -> str:
-        cache_key = ("ClusterRoleBinding", "", name)
-        if self._fresh(cache_key):
-            return name
-        try:
-            crb = await self.client.get(RBAC_API_VERSION, "ClusterRoleBinding", "", name)
-            self._mark(cache_key)
-            return crb["metadata"]["name"]
-        except NotFoundError:
-            pass
-        crb = {
-            "apiVersion": RBAC_API_VERSION,
-            "kind": "ClusterRoleBinding",
-            "metadata": {"name": name, "labels": _managed_labels()},
-            "roleRef": {
-                "apiGroup": "rbac.authorization.k8s.io",
-                "kind": "ClusterRole",
-                "name": role_name,
-            },
-            "subjects": [
-                {"kind": "ServiceAccount", "name": sa_name, "namespace": sa_namespace}
-            ],
-        }
-        try:
-            created = await self.client.create(crb, transfer=True)
-        except AlreadyExistsError:
-            # concurrent reconciles sharing an SA race get-then-create;
-            # losing the race means the object exists — reuse it
-            self._mark(cache_key)
-            return name
-        self._mark(cache_key)
-        return created["metadata"]["name"]
-
-    async def create_namespace_role(
-        self, name: str, namespace: str, rules: List[PolicyRule]
-    ) -> str:
-        cache_key = ("Role", namespace, name)
-        if self._fresh(cache_key):
-            return name
-        try:
-            role = await self.client.get(RBAC_API_VERSION, "Role", namespace, name)
-            self._mark(cache_key)
-            return role["metadata"]["name"]
-        except NotFoundError:
-            pass
-        role = {
-            "apiVersion": RBAC_API_VERSION,
-            "kind": "Role",
-            "metadata": {"name": name, "namespace": namespace, "labels": _managed_labels()},
-            "rules": [r.to_dict() for r in rules],
-        }
-        try:
-            created = await self.client.create(role, transfer=True)
-        except AlreadyExistsError:
-            # concurrent reconciles sharing an SA race get-then-create;
-            # losing the race means the object exists — reuse it
-            self._mark(cache_key)
-            return name
-        self._mark(cache_key)
-        return created["metadata"]["name"]
-
-    async def create_namespace_role_binding(
-        self, name: str, role_name: str, sa_name: str, namespace: str
-    ) -> str:
-        cache_key = ("RoleBinding", namespace, name)
-        if self._fresh(cache_key):
-            return name
-        try:
-            rb = await self.client.get(RBAC_API_VERSION, "RoleBinding", namespace, name)
-            self._mark(cache_key)
-            return rb["metadata"]["name"]
-        except NotFoundError:
-            pass
-        rb = {
-            "apiVersion": RBAC_API_VERSION,
-            "kind": "RoleBinding",
-            "metadata": {"name": name, "namespace": namespace, "labels": _managed_labels()},
-            "roleRef": {
-                "apiGroup": "rbac.authorization.k8s.io",
-                "kind": "Role",
-                "name": role_name,
-            },
-            "subjects": [
-                {"kind": "ServiceAccount", "name": sa_name, "namespace": namespace}
-            ],
-        }
-        try:
-            created = await self.client.create(rb, transfer=True)
-        except AlreadyExistsError:
-            # concurrent reconciles sharing an SA race get-then-create;
-            # losing the race means the object exists — reuse it
-            self._mark(cache_key)
-            return name
-        self._mark(cache_key)
-        return created["metadata"]["name"]
-
-    # -- deletes (only objects carrying the managed-by label) --------------
 
     async def _delete_if_managed(self, api_version: str, kind: str, namespace: str, name: str) -> None:
+        """Drop the TTL-cache entry, then delete the object if it carries the
+        managed-by label."""
+        self._ensured.pop((kind, namespace, name), None)
         # Already-gone objects count as deleted. (The reference propagates the
         # Get error here (:1164-1166), which makes concurrent remedy teardowns
         # of a shared SA fail each other — an availability fix, not a
@@ -301,98 +179,61 @@ class RBACProvisioner:
             except NotFoundError:
                 return
 
-    async def delete_service_account(self, name: str, namespace: str) -> None:
-        self._invalidate("ServiceAccount", namespace, name)
-        await self._delete_if_managed("v1", "ServiceAccount", namespace, name)
-
-    async def delete_cluster_role(self, name: str) -> None:
-        self._invalidate("ClusterRole", "", name)
-        await self._delete_if_managed(RBAC_API_VERSION, "ClusterRole", "", name)
-
-    async def delete_cluster_role_binding(self, name: str) -> None:
-        self._invalidate("ClusterRoleBinding", "", name)
-        await self._delete_if_managed(RBAC_API_VERSION, "ClusterRoleBinding", "", name)
-
-    async def delete_namespace_role(self, name: str, namespace: str) -> None:
-        self._invalidate("Role", namespace, name)
-        await self._delete_if_managed(RBAC_API_VERSION, "Role", namespace, name)
-
-    async def delete_namespace_role_binding(self, name: str, namespace: str) -> None:
-        self._invalidate("RoleBinding", namespace, name)
-        await self._delete_if_managed(RBAC_API_VERSION, "RoleBinding", namespace, name)
-
     # -- orchestration ------------------------------------------------------
 
     async def create_rbac_for_workflow(self, hc: HealthCheck, workflow_type: str) -> None:
         """``workflow_type`` ∈ {"healthCheck", "remedy"}
         (healthcheck_controller.go:302-415). May rename the remedy SA on
         collision — a spec mutation visible for the rest of the reconcile,
-        as in the reference (:316-319)."""
-        hc_obj = hc.to_dict()
-        level = hc.spec.level
-        hc_sa = hc.spec.workflow.resource.service_account
-        wf_namespace = hc.spec.workflow.resource.namespace
+        as in the reference (:316-319). The remedy is validated (and renamed)
+        whichever of the two is being provisioned."""
+        check, remedy = hc.spec.workflow, hc.spec.remedy_workflow
+        sa, ns = check.resource.service_account, check.resource.namespace
+        rules = resolve_rbac_rules(check.rbac_rules, DEFAULT_HEALTHCHECK_RULES)
 
-        remedy_sa = ""
-        wf_remedy_namespace = ""
-        if not hc.spec.remedy_workflow.is_empty():
-            if hc.spec.remedy_workflow.resource is None:
+        remedy_sa = remedy_ns = ""
+        if not remedy.is_empty():
+            if remedy.resource is None:
                 await self._event(hc.to_dict(), "Warning",
                                   "RemedyWorkflow is set but Resource is nil")
                 raise ValueError("RemedyWorkflow is set but Resource is nil")
-            if hc.spec.remedy_workflow.resource.service_account == "":
+            if remedy.resource.service_account == "":
                 await self._event(
                     hc.to_dict(), "Warning",
                     "ServiceAccount for the RemedyWorkflow is not specified"
                 )
                 raise ValueError("ServiceAccount for the RemedyWorkflow is not specified")
-            if hc_sa == hc.spec.remedy_workflow.resource.service_account:
-                hc.spec.remedy_workflow.resource.service_account = hc_sa + "-remedy"
-            remedy_sa = hc.spec.remedy_workflow.resource.service_account
-            wf_remedy_namespace = hc.spec.remedy_workflow.resource.namespace
+            if sa == remedy.resource.service_account:
+                remedy.resource.service_account = sa + "-remedy"
+            remedy_sa, remedy_ns = remedy.resource.service_account, remedy.resource.namespace
 
-        is_remedy = workflow_type == "remedy"
-        if is_remedy:
-            await self.create_service_account(remedy_sa, wf_remedy_namespace)
-        else:
-            await self.create_service_account(hc_sa, wf_namespace)
+        if workflow_type == "remedy":
+            sa, ns = remedy_sa, remedy_ns
+            rules = resolve_rbac_rules(remedy.rbac_rules, DEFAULT_REMEDY_RULES)
 
-        hc_rules = resolve_rbac_rules(hc.spec.workflow.rbac_rules, DEFAULT_HEALTHCHECK_RULES)
-        remedy_rules = resolve_rbac_rules(hc.spec.remedy_workflow.rbac_rules, DEFAULT_REMEDY_RULES)
-
-        if level == CLUSTER_LEVEL:
-            if not is_remedy:
-                await self.create_cluster_role(hc_sa + "-cluster-role", hc_rules)
-                await self.create_cluster_role_binding(
-                    hc_sa + "-cluster-role-binding", hc_sa + "-cluster-role", hc_sa, wf_namespace
-                )
-            else:
-                await self.create_cluster_role(remedy_sa + "-cluster-role", remedy_rules)
-                await self.create_cluster_role_binding(
-                    remedy_sa + "-cluster-role-binding",
-                    remedy_sa + "-cluster-role",
-                    remedy_sa,
-                    wf_remedy_namespace,
-                )
-        elif level == NAMESPACE_LEVEL:
-            if not is_remedy:
-                await self.create_namespace_role(hc_sa + "-ns-role", wf_namespace, hc_rules)
-                await self.create_namespace_role_binding(
-                    hc_sa + "-ns-role-binding", hc_sa + "-ns-role", hc_sa, wf_namespace
-                )
-            else:
-                await self.create_namespace_role(
-                    remedy_sa + "-ns-role", wf_remedy_namespace, remedy_rules
-                )
-                await self.create_namespace_role_binding(
-                    remedy_sa + "-ns-role-binding",
-                    remedy_sa + "-ns-role",
-                    remedy_sa,
-                    wf_remedy_namespace,
-                )
-        else:
+        # the SA is created before an unset level is reported (:333-345)
+        await self._ensure("v1", "ServiceAccount", ns, sa)
+        role = _ROLE_BY_LEVEL.get(hc.spec.level)
+        if role is None:
             await self._event(hc.to_dict(), "Warning", "level is not set")
             raise ValueError("level is not set")
+        role_kind, suffix = role
+        role_ns = "" if role_kind == "ClusterRole" else ns
+        await self._ensure(
+            RBAC_API_VERSION, role_kind, role_ns, sa + suffix,
+            lambda: {"rules": [r.to_dict() for r in rules]},
+        )
+        await self._ensure(
+            RBAC_API_VERSION, role_kind + "Binding", role_ns, sa + suffix + "-binding",
+            lambda: {
+                "roleRef": {
+                    "apiGroup": "rbac.authorization.k8s.io",
+                    "kind": role_kind,
+                    "name": sa + suffix,
+                },
+                "subjects": [{"kind": "ServiceAccount", "name": sa, "namespace": ns}],
+            },
+        )
 
     async def delete_rbac_for_workflow(self, hc: HealthCheck) -> None:
         """Tear down the remedy RBAC after a remedy run
@@ -400,16 +241,15 @@ class RBACProvisioner:
         and only when labeled managed-by active-monitor."""
         if hc.spec.remedy_workflow.resource is None:
             return
-        level = hc.spec.level
-        remedy_sa = hc.spec.remedy_workflow.resource.service_account
+        sa = hc.spec.remedy_workflow.resource.service_account
         ns = hc.spec.remedy_workflow.resource.namespace
-        await self.delete_service_account(remedy_sa, ns)
-        if level == CLUSTER_LEVEL:
-            await self.delete_cluster_role(remedy_sa + "-cluster-role")
-            await self.delete_cluster_role_binding(remedy_sa + "-cluster-role-binding")
-        elif level == NAMESPACE_LEVEL:
-            await self.delete_namespace_role(remedy_sa + "-ns-role", ns)
-            await self.delete_namespace_role_binding(remedy_sa + "-ns-role-binding", ns)
-        else:
+        await self._delete_if_managed("v1", "ServiceAccount", ns, sa)
+        role = _ROLE_BY_LEVEL.get(hc.spec.level)
+        if role is None:
             await self._event(hc.to_dict(), "Warning", "level is not set")
             raise ValueError("level is not set")
+        role_kind, suffix = role
+        role_ns = "" if role_kind == "ClusterRole" else ns
+        await self._delete_if_managed(RBAC_API_VERSION, role_kind, role_ns, sa + suffix)
+        await self._delete_if_managed(
+            RBAC_API_VERSION, role_kind + "Binding", role_ns, sa + suffix + "-binding")

@@ -30,7 +30,7 @@ import asyncio
 import logging
 import time
 from dataclasses import dataclass
-from typing import Any, Dict, Optional, Set, Tuple
+from typing import Any, Awaitable, Dict, Optional, Set, Tuple
 
 from .. import API_VERSION
 from ..api.types import HealthCheck, k8s_now, parse_k8s_time
@@ -47,10 +47,7 @@ from ..metrics import (
 )
 from .backoff import IEBTimeoutError, InverseExponentialBackoff, compute_backoff_params
 from .cronx import CronParseError, seconds_until_next
-from .parse import (
-    parse_remedy_workflow_from_healthcheck_async,
-    parse_workflow_from_healthcheck_async,
-)
+from .parse import parse_from_healthcheck_async
 from .rbac import RBACProvisioner
 from .workqueue import WorkQueue
 
@@ -118,7 +115,7 @@ class HealthCheckReconciler:
         # below the floor fall through to a direct GET. This closes a
         # lost-update race controller-runtime's cached client actually has.
         self._written_rv: Dict[Tuple[str, str], int] = {}
-        self.repeat_timers_by_name: Dict[str, RepeatTimer] = {}
+        self.repeat_timers_by_name: Dict[Tuple[str, str], RepeatTimer] = {}
         self._watch_tasks: Dict[str, Set[asyncio.Task]] = {}
         # observability for benchmarks/tests
         self.reconcile_count = 0
@@ -334,43 +331,37 @@ class HealthCheckReconciler:
             )
             await self.update_healthcheck_status(hc)
             return ReconcileResult()
-        elif not from_timer and self._watch_tasks.get((hc.namespace, hc.name)):
+        if not from_timer and self._watch_tasks.get((hc.namespace, hc.name)):
             # a run for this CR is already in flight: spurious reconciles
             # (informer list/watch overlap at startup, spec edits mid-run)
             # must not submit a duplicate workflow. The reference double-
             # submits here and parks a second blocked goroutine per duplicate
             # (SURVEY.md §2.3.1); the clean rebuild closes that hole.
             return ReconcileResult()
-        elif spec.repeat_after_sec <= 0 and spec.schedule.cron != "":
+        if spec.repeat_after_sec <= 0:
             # cron branch (:251-263): +1s compensates integer truncation
             try:
-                hc.spec.repeat_after_sec = seconds_until_next(spec.schedule.cron)
-            except CronParseError as e:
+                spec.repeat_after_sec = seconds_until_next(spec.schedule.cron)
+            except CronParseError:
                 await self._event(hc, "Warning", "Fail to parse cron")
-                raise e
-            # the reference's elif chain exempts cron CRs from the
-            # already-scheduled dedup, so every status write re-submits them
-            # in a tight loop until the blocking watch throttles it; apply the
-            # dedup here with the freshly computed interval instead
-            if (
-                not from_timer
-                and int(time.time() - finished_unix) < hc.spec.repeat_after_sec
-                and self.get_timer_by_name(hc.name, hc.namespace) is not None
-            ):
-                return ReconcileResult()
-        elif (
+                raise
+        # already executed recently and a repeat is scheduled (:264-267). The
+        # reference's elif chain exempts cron CRs from this dedup, so every
+        # status write re-submits them in a tight loop until the blocking
+        # watch throttles it; here it applies to them too, with the freshly
+        # computed interval
+        if (
             not from_timer
             and int(time.time() - finished_unix) < spec.repeat_after_sec
             and self.get_timer_by_name(hc.name, hc.namespace) is not None
         ):
-            # already executed recently and a repeat is scheduled (:264-267)
             return ReconcileResult()
 
         try:
             await self.rbac.create_rbac_for_workflow(hc, HEALTHCHECK)
-        except Exception as e:
+        except Exception:
             await self._event(hc, "Warning", "Error creating RBAC for HealthCheckWorkflow")
-            raise e
+            raise
 
         generated_name = await self.create_submit_workflow(hc)
         # non-blocking watch: the reconcile worker is freed immediately
@@ -393,54 +384,57 @@ class HealthCheckReconciler:
             "controller": True,
         }
 
-    async def create_submit_workflow(self, hc: HealthCheck) -> str:
+    #: (parse/submit error, parsed, created) event texts; the remedy's
+    #: spellings are the reference's (:515-568)
+    _SUBMIT_EVENTS = (
+        "Error creating or submitting workflow",
+        "workflow is parsed from healthcheck",
+        "Successfully created workflow",
+    )
+    _REMEDY_SUBMIT_EVENTS = (
+        "Error creating or submitting remedyworkflow",
+        "Remedy workflow is parsed from healthcheck",
+        "Successfully created remedyWorkflow",
+    )
+
+    async def _create_submit(self, hc: HealthCheck, remedy: bool) -> str:
+        """Parse ``spec.workflow`` (or ``spec.remedyworkflow``) and create the
+        Workflow; returns its generated name."""
+        wf_spec = hc.spec.remedy_workflow if remedy else hc.spec.workflow
+        if remedy and wf_spec.resource is None:
+            raise ValueError("RemedyWorkflow Resource is nil")
+        failed, parsed, created_ok = (
+            self._REMEDY_SUBMIT_EVENTS if remedy else self._SUBMIT_EVENTS
+        )
         try:
-            spec, labels = await parse_workflow_from_healthcheck_async(hc)
-        except Exception as e:
-            await self._event(hc, "Warning", "Error creating or submitting workflow")
-            raise e
-        await self._event(hc, "Normal", "workflow is parsed from healthcheck")
+            spec, labels = await parse_from_healthcheck_async(hc, remedy)
+        except Exception:
+            await self._event(hc, "Warning", failed)
+            raise
+        await self._event(hc, "Normal", parsed)
         wf = {
             "apiVersion": WF_API_VERSION,
             "kind": WF_KIND,
             "metadata": {
-                "generateName": hc.spec.workflow.generate_name,
-                "namespace": hc.spec.workflow.resource.namespace,
+                "generateName": wf_spec.generate_name,
+                "namespace": wf_spec.resource.namespace,
                 "labels": labels,
                 "ownerReferences": [self._owner_reference(hc)],
             },
             "spec": spec,
         }
         created = await self.client.create(wf, transfer=True)
-        await self._event(hc, "Normal", "Successfully created workflow")
+        await self._event(hc, "Normal", created_ok)
         return created["metadata"]["name"]
 
-    async def create_submit_remedy_workflow(self, hc: HealthCheck) -> str:
-        if hc.spec.remedy_workflow.resource is None:
-            raise ValueError("RemedyWorkflow Resource is nil")
-        try:
-            spec, labels = await parse_remedy_workflow_from_healthcheck_async(hc)
-        except Exception as e:
-            await self._event(hc, "Warning", "Error creating or submitting remedyworkflow")
-            raise e
-        await self._event(hc, "Normal", "Remedy workflow is parsed from healthcheck")
-        wf = {
-            "apiVersion": WF_API_VERSION,
-            "kind": WF_KIND,
-            "metadata": {
-                "generateName": hc.spec.remedy_workflow.generate_name,
-                "namespace": hc.spec.remedy_workflow.resource.namespace,
-                "labels": labels,
-                "ownerReferences": [self._owner_reference(hc)],
-            },
-            "spec": spec,
-        }
-        created = await self.client.create(wf, transfer=True)
-        await self._event(hc, "Normal", "Successfully created remedyWorkflow")
-        return created["metadata"]["name"]
+    def create_submit_workflow(self, hc: HealthCheck) -> Awaitable[str]:
+        return self._create_submit(hc, remedy=False)
+
+    def create_submit_remedy_workflow(self, hc: HealthCheck) -> Awaitable[str]:
+        return self._create_submit(hc, remedy=True)
 
     # ------------------------------------------------------------------
-    # Watch: health-check workflow (reference :607-757)
+    # Watch (reference :607-757 health check, :788-874 remedy)
     # ------------------------------------------------------------------
 
     _POLL_RETRIES = 3
@@ -507,20 +501,19 @@ class HealthCheckReconciler:
         ieb.check_deadline()
         return changed is not None
 
-    async def watch_workflow_reschedule(
-        self, wf_namespace: str, wf_name: str, hc: HealthCheck
-    ) -> None:
-        then = k8s_now()
-        then_unix = time.time()
-        repeat_after_sec = hc.spec.repeat_after_sec
-        max_t, min_t, factor, timeout = compute_backoff_params(
-            hc.spec.backoff_max, hc.spec.backoff_min, hc.spec.backoff_factor,
-            hc.spec.workflow.timeout,
-        )
+    async def _watch_until_terminal(
+        self, hc: HealthCheck, wf_namespace: str, wf_name: str,
+        backoff: Tuple[float, float, float, float], timeout_event: str,
+    ) -> Optional[Dict[str, Any]]:
+        """Poll a workflow until it is Succeeded or Failed and return its
+        status, or None once it no longer exists (:618-622). ``backoff`` is
+        ``(max, min, timeout, factor)`` in seconds; past the timeout the
+        status is synthesized as ``{phase: Failed, message: Failed}`` and
+        ``timeout_event`` is emitted (:627-632)."""
         ieb: Optional[InverseExponentialBackoff] = None
         timed_out = False
         try:
-            ieb = InverseExponentialBackoff(max_t, min_t, timeout, factor)
+            ieb = InverseExponentialBackoff(*backoff)
         except ValueError:
             # invalid params (e.g. timeout 0): the reference's loop sees a
             # constructor error on its first iteration and synthesizes Failed
@@ -537,92 +530,218 @@ class HealthCheckReconciler:
                 status = await self._poll_workflow(wf_namespace, wf_name,
                                                    via_cache=via_cache)
             except NotFoundError:
-                # parent healthcheck likely deleted; don't reschedule (:618-622)
-                await self._event(
-                    hc,
-                    "Warning",
-                    "Error attempting to find workflow for healthcheck. This may "
-                    "indicate that either the healthcheck was removed or the Workflow "
-                    "was GC'd before active-monitor could obtain the status",
-                )
-                if self.wf_hub is not None:
-                    self.wf_hub.forget(wf_namespace, wf_name)
-                return
+                status = None
+                break
             if timed_out:
                 status = {"phase": FAIL_STR, "message": FAIL_STR}
-                await self._event(hc, "Warning", "Workflow timed out")
-            if status is not None:
-                phase = status.get("phase")
-                now = k8s_now()
-                now_unix = time.time()
-                if phase == SUCC_STR:
-                    await self._event(hc, "Normal", "Workflow status is Succeeded")
-                    hc.status.status = SUCC_STR
-                    hc.status.started_at = then
-                    hc.status.finished_at = now
-                    hc.status.success_count += 1
-                    hc.status.total_healthcheck_runs = (
-                        hc.status.success_count + hc.status.failed_count
-                    )
-                    hc.status.last_successful_workflow = wf_name
-                    MonitorSuccess.labels(hc.name, HEALTHCHECK).inc()
-                    MonitorRuntime.labels(hc.name, HEALTHCHECK).set(now_unix - then_unix)
-                    MonitorStartedTime.labels(hc.name, HEALTHCHECK).set(int(then_unix))
-                    MonitorFinishedTime.labels(hc.name, HEALTHCHECK).set(int(now_unix))
-                    # custom metrics from workflow output parameters — the
-                    # reference documents this (README.md:275-285) but never
-                    # wires it; here the documented feature is real.
-                    create_dynamic_prometheus_metric(hc.name, status)
-                    if (
-                        not hc.spec.remedy_workflow.is_empty()
-                        and hc.status.remedy_total_runs >= 1
-                    ):
-                        hc.status.reset_remedy()
-                        hc.status.remedy_status = "HealthCheck Passed so Remedy is reset"
-                        await self._event(hc, "Normal", "HealthCheck passed so Remedy is reset")
-                    break
-                elif phase == FAIL_STR:
-                    await self._event(hc, "Warning", "Workflow status is Failed")
-                    hc.status.status = FAIL_STR
-                    hc.status.started_at = then
-                    hc.status.finished_at = now
-                    hc.status.last_failed_at = now
-                    msg = status.get("message")
-                    hc.status.error_message = msg if isinstance(msg, str) else ""
-                    hc.status.failed_count += 1
-                    hc.status.total_healthcheck_runs = (
-                        hc.status.success_count + hc.status.failed_count
-                    )
-                    hc.status.last_failed_workflow = wf_name
-                    MonitorError.labels(hc.name, HEALTHCHECK).inc()
-                    MonitorStartedTime.labels(hc.name, HEALTHCHECK).set(int(then_unix))
-                    MonitorFinishedTime.labels(hc.name, HEALTHCHECK).set(int(now_unix))
-                    try:
-                        await self._maybe_run_remedy(hc, now_unix)
-                    except asyncio.CancelledError:
-                        raise
-                    except Exception as e:
-                        # a remedy failure must not lose the health-check
-                        # status or the repeat schedule (the reference aborts
-                        # the whole watch here, stalling the CR — :686-688)
-                        log.warning("remedy for %s failed: %s", hc.name, e)
-                        await self._event(hc, "Warning", "Error executing RemedyWorkflow")
-                    break
+                await self._event(hc, "Warning", timeout_event)
+                break
+            if status is not None and status.get("phase") in (SUCC_STR, FAIL_STR):
+                break
             # not terminal yet: wait for the next poll (hub-accelerated)
             try:
                 via_cache = await self._wait_next_poll(ieb, wf_namespace, wf_name, seq)
             except IEBTimeoutError:
                 timed_out = True
+        # this watch is done with the workflow forever (names are unique):
+        # release its hub cache/seq entry now rather than waiting for the
+        # server-side TTL delete (RSS leak at fleet rates otherwise)
+        if self.wf_hub is not None:
+            self.wf_hub.forget(wf_namespace, wf_name)
+        return status
 
+    async def watch_workflow_reschedule(
+        self, wf_namespace: str, wf_name: str, hc: HealthCheck
+    ) -> None:
+        then = k8s_now()
+        then_unix = time.time()
+        repeat_after_sec = hc.spec.repeat_after_sec
+        max_t, min_t, factor, timeout = compute_backoff_params(
+            hc.spec.backoff_max, hc.spec.backoff_min, hc.spec.backoff_factor,
+            hc.spec.workflow.timeout,
+        )
+        status = await self._watch_until_terminal(
+            hc, wf_namespace, wf_name, (max_t, min_t, timeout, factor),
+            "Workflow timed out",
+        )
+        if status is None:
+            # parent healthcheck likely deleted; don't reschedule (:618-622)
+            await self._event(
+                hc,
+                "Warning",
+                "Error attempting to find workflow for healthcheck. This may "
+                "indicate that either the healthcheck was removed or the Workflow "
+                "was GC'd before active-monitor could obtain the status",
+            )
+            return
+        await self._apply_check_result(hc, wf_name, status, then, then_unix)
         try:
-            await self._finish_and_reschedule(hc, wf_namespace, wf_name, repeat_after_sec)
+            await self._finish_and_reschedule(hc, repeat_after_sec)
         finally:
-            # this watch is done with the workflow forever (names are unique):
-            # release its hub cache/seq entry now rather than waiting for the
-            # server-side TTL delete (RSS leak at fleet rates otherwise)
-            if self.wf_hub is not None:
-                self.wf_hub.forget(wf_namespace, wf_name)
             self.completed_runs += 1
+
+    async def watch_remedy_workflow(
+        self, wf_namespace: str, wf_name: str, hc: HealthCheck
+    ) -> None:
+        """Remedy watch (reference :788-874): backoff params derive from the
+        *health-check* workflow's timeout with factor fixed at 0.5 (:791-801),
+        a reference quirk kept for behavioral parity. A vanished remedy
+        workflow ends the watch silently."""
+        then = k8s_now()
+        then_unix = time.time()
+        max_t, min_t, _factor, timeout = compute_backoff_params(
+            0, 0, "", hc.spec.workflow.timeout
+        )
+        status = await self._watch_until_terminal(
+            hc, wf_namespace, wf_name, (max_t, min_t, timeout, 0.5),
+            "remedy workflow is timedout",
+        )
+        if status is None:
+            return
+        await self._apply_remedy_result(hc, wf_name, status, then, then_unix)
+        # persist remedy status promptly (reference :856-871); the check's
+        # own write follows when its watch finishes
+        fresh = await self._get_live_hc(hc)
+        if fresh is not None:
+            await self.update_healthcheck_status(hc, fresh=fresh)
+
+    # ------------------------------------------------------------------
+    # Status + metric mutations for a terminal workflow: check, then remedy
+    # ------------------------------------------------------------------
+
+    async def _apply_check_result(
+        self, hc: HealthCheck, wf_name: str, status: Dict[str, Any],
+        then: str, then_unix: float,
+    ) -> None:
+        """Reference :634-727. Only the check registers custom metrics,
+        resets the remedy on a pass and triggers it on a failure."""
+        st = hc.status
+        now = k8s_now()
+        now_unix = time.time()
+        if status.get("phase") == SUCC_STR:
+            await self._event(hc, "Normal", "Workflow status is Succeeded")
+            st.status = SUCC_STR
+            st.started_at = then
+            st.finished_at = now
+            st.success_count += 1
+            st.total_healthcheck_runs = st.success_count + st.failed_count
+            st.last_successful_workflow = wf_name
+            MonitorSuccess.labels(hc.name, HEALTHCHECK).inc()
+            MonitorRuntime.labels(hc.name, HEALTHCHECK).set(now_unix - then_unix)
+            MonitorStartedTime.labels(hc.name, HEALTHCHECK).set(int(then_unix))
+            MonitorFinishedTime.labels(hc.name, HEALTHCHECK).set(int(now_unix))
+            # custom metrics from workflow output parameters — the
+            # reference documents this (README.md:275-285) but never
+            # wires it; here the documented feature is real.
+            create_dynamic_prometheus_metric(hc.name, status)
+            if not hc.spec.remedy_workflow.is_empty() and st.remedy_total_runs >= 1:
+                st.reset_remedy()
+                st.remedy_status = "HealthCheck Passed so Remedy is reset"
+                await self._event(hc, "Normal", "HealthCheck passed so Remedy is reset")
+        else:
+            await self._event(hc, "Warning", "Workflow status is Failed")
+            st.status = FAIL_STR
+            st.started_at = then
+            st.finished_at = now
+            st.last_failed_at = now
+            msg = status.get("message")
+            st.error_message = msg if isinstance(msg, str) else ""
+            st.failed_count += 1
+            st.total_healthcheck_runs = st.success_count + st.failed_count
+            st.last_failed_workflow = wf_name
+            MonitorError.labels(hc.name, HEALTHCHECK).inc()
+            MonitorStartedTime.labels(hc.name, HEALTHCHECK).set(int(then_unix))
+            MonitorFinishedTime.labels(hc.name, HEALTHCHECK).set(int(now_unix))
+            try:
+                await self._maybe_run_remedy(hc, now_unix)
+            except asyncio.CancelledError:
+                raise
+            except Exception as e:
+                # a remedy failure must not lose the health-check
+                # status or the repeat schedule (the reference aborts
+                # the whole watch here, stalling the CR — :686-688)
+                log.warning("remedy for %s failed: %s", hc.name, e)
+                await self._event(hc, "Warning", "Error executing RemedyWorkflow")
+
+    async def _apply_remedy_result(
+        self, hc: HealthCheck, wf_name: str, status: Dict[str, Any],
+        then: str, then_unix: float,
+    ) -> None:
+        """Reference :819-855. The remedy_* twins of the check's fields —
+        except the two reference quirks marked below."""
+        st = hc.status
+        now = k8s_now()
+        now_unix = time.time()
+        if status.get("phase") == SUCC_STR:
+            await self._event(hc, "Normal", "Remedy workflow status is Succeeded")
+            st.remedy_status = SUCC_STR
+            st.remedy_started_at = then
+            st.remedy_finished_at = now
+            st.remedy_success_count += 1
+            st.remedy_total_runs = st.remedy_success_count + st.remedy_failed_count
+            # reference quirk kept: remedy watch writes the shared
+            # last*Workflow fields with the remedy name (:830)
+            st.last_successful_workflow = wf_name
+            MonitorSuccess.labels(hc.name, REMEDY).inc()
+            MonitorRuntime.labels(hc.name, REMEDY).set(now_unix - then_unix)
+            MonitorStartedTime.labels(hc.name, REMEDY).set(int(then_unix))
+            # reference quirk kept: finished-time gauge carries the
+            # HEALTH-CHECK finish epoch, not the remedy's (:834)
+            hc_fin = parse_k8s_time(st.finished_at)
+            MonitorFinishedTime.labels(hc.name, REMEDY).set(
+                int(hc_fin.timestamp()) if hc_fin else int(now_unix)
+            )
+        else:
+            await self._event(hc, "Warning", "remedy workflow status is failed")
+            st.remedy_status = FAIL_STR
+            st.remedy_started_at = then
+            st.remedy_finished_at = now
+            st.remedy_last_failed_at = now
+            msg = status.get("message")
+            st.remedy_error_message = msg if isinstance(msg, str) else ""
+            st.remedy_failed_count += 1
+            st.remedy_total_runs = st.remedy_success_count + st.remedy_failed_count
+            st.last_failed_workflow = wf_name
+            MonitorError.labels(hc.name, REMEDY).inc()
+            MonitorStartedTime.labels(hc.name, REMEDY).set(int(then_unix))
+            MonitorFinishedTime.labels(hc.name, REMEDY).set(int(now_unix))
+
+    async def _finish_and_reschedule(self, hc: HealthCheck, repeat_after_sec: float) -> None:
+        """Persist status and re-arm the repeat timer (reference :729-757).
+
+        The timer is armed BEFORE the status write so the MODIFIED event the
+        write triggers always observes an armed timer in the dedup branch —
+        closing a duplicate-submission race the reference leaves open by
+        updating first (:734) and arming after (:746)."""
+        fresh = await self._get_live_hc(hc)
+        if fresh is None:
+            return
+        # cron CRs: recompute the delay at completion time so the next run
+        # lands on the cron tick, not submit-time + interval (the reference
+        # re-arms with the stale submit-time value, drifting by the run's
+        # duration — :746-752)
+        fresh_spec = fresh.get("spec") or {}
+        cron = ((fresh_spec.get("schedule") or {}).get("cron")) or ""
+        if int(fresh_spec.get("repeatAfterSec", 0) or 0) <= 0 and cron:
+            try:
+                repeat_after_sec = seconds_until_next(cron)
+            except CronParseError:
+                pass  # keep the submit-time value
+        self._arm_repeat_timer(hc.name, hc.namespace, repeat_after_sec)
+        try:
+            await self.update_healthcheck_status(hc, fresh=fresh)
+        except NotFoundError:
+            self._stop_timer(hc.name, hc.namespace)
+            return
+        except Exception:
+            await self._event(hc, "Warning", "Error updating healthcheck resource")
+            self._stop_timer(hc.name, hc.namespace)
+            raise
+        await self._event(hc, "Normal", "Rescheduled workflow for next run")
+
+    # ------------------------------------------------------------------
+    # Remedy (reference :677-721, :759-786)
+    # ------------------------------------------------------------------
 
     async def _maybe_run_remedy(self, hc: HealthCheck, now_unix: float) -> None:
         """The remedy trigger state machine (reference :677-721)."""
@@ -651,48 +770,6 @@ class HealthCheckReconciler:
         else:
             await self.process_remedy_workflow(hc)
 
-    async def _finish_and_reschedule(
-        self, hc: HealthCheck, wf_namespace: str, wf_name: str, repeat_after_sec: float
-    ) -> None:
-        """Persist status and re-arm the repeat timer (reference :729-757).
-
-        The timer is armed BEFORE the status write so the MODIFIED event the
-        write triggers always observes an armed timer in the dedup branch —
-        closing a duplicate-submission race the reference leaves open by
-        updating first (:734) and arming after (:746)."""
-        try:
-            fresh = await self._get_hc(hc.namespace, hc.name)
-        except NotFoundError:
-            return
-        if (fresh.get("metadata") or {}).get("deletionTimestamp"):
-            return
-        # cron CRs: recompute the delay at completion time so the next run
-        # lands on the cron tick, not submit-time + interval (the reference
-        # re-arms with the stale submit-time value, drifting by the run's
-        # duration — :746-752)
-        fresh_spec = fresh.get("spec") or {}
-        cron = ((fresh_spec.get("schedule") or {}).get("cron")) or ""
-        if int(fresh_spec.get("repeatAfterSec", 0) or 0) <= 0 and cron:
-            try:
-                repeat_after_sec = seconds_until_next(cron)
-            except CronParseError:
-                pass  # keep the submit-time value
-        self._arm_repeat_timer(hc.name, hc.namespace, repeat_after_sec)
-        try:
-            await self.update_healthcheck_status(hc, fresh=fresh)
-        except NotFoundError:
-            self._stop_timer(hc.name, hc.namespace)
-            return
-        except Exception as e:
-            await self._event(hc, "Warning", "Error updating healthcheck resource")
-            self._stop_timer(hc.name, hc.namespace)
-            raise e
-        await self._event(hc, "Normal", "Rescheduled workflow for next run")
-
-    # ------------------------------------------------------------------
-    # Remedy (reference :759-874)
-    # ------------------------------------------------------------------
-
     async def process_remedy_workflow(self, hc: HealthCheck) -> None:
         """create remedy RBAC → submit → watch → delete remedy RBAC
         (reference :759-786)."""
@@ -705,99 +782,20 @@ class HealthCheckReconciler:
         await self.watch_remedy_workflow(remedy_ns, generated_name, hc)
         await self.rbac.delete_rbac_for_workflow(hc)
 
-    async def watch_remedy_workflow(
-        self, wf_namespace: str, wf_name: str, hc: HealthCheck
-    ) -> None:
-        """Remedy watch loop (reference :788-874): backoff params derive from
-        the *health-check* workflow's timeout with factor fixed at 0.5
-        (:791-801), a reference quirk kept for behavioral parity."""
-        then = k8s_now()
-        then_unix = time.time()
-        max_t, min_t, _factor, timeout = compute_backoff_params(
-            0, 0, "", hc.spec.workflow.timeout
-        )
-        ieb: Optional[InverseExponentialBackoff] = None
-        timed_out = False
-        try:
-            ieb = InverseExponentialBackoff(max_t, min_t, timeout, 0.5)
-        except ValueError:
-            timed_out = True
-
-        via_cache = self.wf_hub is not None
-        while True:
-            seq = self.wf_hub.seq(wf_namespace, wf_name) if self.wf_hub else None
-            try:
-                status = await self._poll_workflow(wf_namespace, wf_name,
-                                                   via_cache=via_cache)
-            except NotFoundError:
-                if self.wf_hub is not None:
-                    self.wf_hub.forget(wf_namespace, wf_name)
-                return
-            if timed_out:
-                status = {"phase": FAIL_STR, "message": FAIL_STR}
-                await self._event(hc, "Warning", "remedy workflow is timedout")
-            if status is not None:
-                phase = status.get("phase")
-                now = k8s_now()
-                now_unix = time.time()
-                if phase == SUCC_STR:
-                    await self._event(hc, "Normal", "Remedy workflow status is Succeeded")
-                    hc.status.remedy_status = SUCC_STR
-                    hc.status.remedy_started_at = then
-                    hc.status.remedy_finished_at = now
-                    hc.status.remedy_success_count += 1
-                    hc.status.remedy_total_runs = (
-                        hc.status.remedy_success_count + hc.status.remedy_failed_count
-                    )
-                    # reference quirk kept: remedy watch writes the shared
-                    # last*Workflow fields with the remedy name (:830)
-                    hc.status.last_successful_workflow = wf_name
-                    MonitorSuccess.labels(hc.name, REMEDY).inc()
-                    MonitorRuntime.labels(hc.name, REMEDY).set(now_unix - then_unix)
-                    MonitorStartedTime.labels(hc.name, REMEDY).set(int(then_unix))
-                    # reference quirk kept: finished-time gauge carries the
-                    # HEALTH-CHECK finish epoch, not the remedy's (:834)
-                    hc_fin = parse_k8s_time(hc.status.finished_at)
-                    MonitorFinishedTime.labels(hc.name, REMEDY).set(
-                        int(hc_fin.timestamp()) if hc_fin else int(now_unix)
-                    )
-                    break
-                elif phase == FAIL_STR:
-                    await self._event(hc, "Warning", "remedy workflow status is failed")
-                    hc.status.remedy_status = FAIL_STR
-                    hc.status.remedy_started_at = then
-                    hc.status.remedy_finished_at = now
-                    hc.status.remedy_last_failed_at = now
-                    msg = status.get("message")
-                    hc.status.remedy_error_message = msg if isinstance(msg, str) else ""
-                    hc.status.remedy_failed_count += 1
-                    hc.status.remedy_total_runs = (
-                        hc.status.remedy_success_count + hc.status.remedy_failed_count
-                    )
-                    hc.status.last_failed_workflow = wf_name
-                    MonitorError.labels(hc.name, REMEDY).inc()
-                    MonitorStartedTime.labels(hc.name, REMEDY).set(int(then_unix))
-                    MonitorFinishedTime.labels(hc.name, REMEDY).set(int(now_unix))
-                    break
-            try:
-                via_cache = await self._wait_next_poll(ieb, wf_namespace, wf_name, seq)
-            except IEBTimeoutError:
-                timed_out = True
-
-        if self.wf_hub is not None:  # done with this workflow forever
-            self.wf_hub.forget(wf_namespace, wf_name)
-        # persist remedy status promptly (reference :856-871)
-        try:
-            fresh = await self._get_hc(hc.namespace, hc.name)
-        except NotFoundError:
-            return
-        if (fresh.get("metadata") or {}).get("deletionTimestamp"):
-            return
-        await self.update_healthcheck_status(hc, fresh=fresh)
-
     # ------------------------------------------------------------------
     # Status persistence (reference :1445-1462)
     # ------------------------------------------------------------------
+
+    async def _get_live_hc(self, hc: HealthCheck) -> Optional[Dict[str, Any]]:
+        """Fresh read for a status write; None when the CR is gone or being
+        deleted, in which case nothing is written."""
+        try:
+            fresh = await self._get_hc(hc.namespace, hc.name)
+        except NotFoundError:
+            return None
+        if (fresh.get("metadata") or {}).get("deletionTimestamp"):
+            return None
+        return fresh
 
     async def update_healthcheck_status(
         self, hc: HealthCheck, retries: int = 5,
