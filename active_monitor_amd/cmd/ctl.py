@@ -22,6 +22,7 @@ import yaml
 
 from .. import API_VERSION
 from ..api.types import parse_k8s_time
+from ..kube.config import get_config
 from ..kube.errors import AlreadyExistsError, ConflictError, NotFoundError
 from ..kube.http import HttpClient
 from ..kube.registry import WF_API_VERSION
@@ -149,6 +150,8 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="amctl", description=__doc__.splitlines()[0])
     p.add_argument("--server", required=True, help="apiserver URL")
     p.add_argument("--token", default="")
+    p.add_argument("--token-file", default=None,
+                   help="read the bearer token from this file")
     p.add_argument("--insecure-skip-tls-verify", action="store_true")
     sub = p.add_subparsers(dest="command", required=True)
 
@@ -174,8 +177,11 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 async def run(args) -> int:
-    client = HttpClient(args.server, token=args.token or None,
-                        verify=not args.insecure_skip_tls_verify)
+    client = get_config(
+        server=args.server, token=args.token,
+        insecure=args.insecure_skip_tls_verify,
+        token_file=getattr(args, "token_file", None),
+    ).make_client()
     await client.start()
     try:
         handler = {"get": cmd_get, "describe": cmd_describe,

@@ -68,6 +68,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kubeconfig", default=None,
                    help="explicit kubeconfig path for --backend http")
     p.add_argument("--token", default="", help="bearer token for --backend http")
+    p.add_argument("--token-file", default=None,
+                   help="with --server: read the bearer token from this file "
+                        "and re-read it as it rotates")
     p.add_argument("--insecure-skip-tls-verify", action="store_true")
     p.add_argument("--workflow-engine", choices=["local", "none"], default="local",
                    help="memory backend: execute workflows locally or leave to an "
@@ -137,6 +140,7 @@ async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         cfg = get_config(
             server=args.server, token=args.token,
             insecure=args.insecure_skip_tls_verify, kubeconfig=args.kubeconfig,
+            token_file=getattr(args, "token_file", None),
         )
         client = cfg.make_client()
         await client.start()

@@ -6,6 +6,7 @@ from .errors import (
     ConflictError,
     InvalidError,
     NotFoundError,
+    UnauthorizedError,
     contains_equal_fold_substring,
     ignore_not_found,
     is_conflict,
@@ -30,6 +31,7 @@ __all__ = [
     "Registry",
     "ResourceInfo",
     "Subscription",
+    "UnauthorizedError",
     "WF_API_VERSION",
     "WF_KIND",
     "WF_PLURAL",

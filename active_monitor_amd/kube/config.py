@@ -6,12 +6,20 @@ apiserver coordinates and credentials from, in order,
 1. an explicit server URL (flags),
 2. the in-cluster service-account mount
    (``/var/run/secrets/kubernetes.io/serviceaccount``),
-3. ``$KUBECONFIG`` / ``~/.kube/config`` (current-context; bearer token or
-   client-certificate auth, cluster CA, insecure-skip-tls-verify).
+3. ``$KUBECONFIG`` / ``~/.kube/config`` (current-context; bearer token,
+   ``tokenFile``, ``exec`` credential plugin or client-certificate auth,
+   cluster CA, insecure-skip-tls-verify).
+
+Credentials that can change while the process runs (the projected
+service-account token, ``tokenFile``, ``exec``) travel as a
+``CredentialSource`` (kube/auth.py) that the client consults per request.
+Not supported: exec plugins that issue client certificates, and the legacy
+``auth-provider`` stanza (a warning says to migrate to ``exec``).
 """
 from __future__ import annotations
 
 import base64
+import logging
 import os
 import tempfile
 from dataclasses import dataclass
@@ -20,11 +28,12 @@ from typing import Optional
 
 import yaml
 
+from .auth import CredentialSource, ExecPluginSource, TokenFileSource
+from .errors import ConfigError  # noqa: F401  (public here)
+
+log = logging.getLogger("active_monitor_amd.kube.config")
+
 SA_DIR = Path("/var/run/secrets/kubernetes.io/serviceaccount")
-
-
-class ConfigError(Exception):
-    pass
 
 
 @dataclass
@@ -35,6 +44,10 @@ class ClusterConfig:
     client_cert_path: Optional[str] = None
     client_key_path: Optional[str] = None
     verify: bool = True
+    #: where ``token`` came from, when a file that is rewritten in place
+    token_file: Optional[str] = None
+    #: rotating credentials; None = ``token`` (or nothing) for good
+    credential_source: Optional[CredentialSource] = None
 
     def make_client(self):
         from .http import HttpClient
@@ -44,6 +57,7 @@ class ClusterConfig:
             token=self.token,
             verify=self.verify,
             ca_cert=self.ca_cert_path,
+            credentials=self.credential_source,
         )
         client.client_cert = (self.client_cert_path, self.client_key_path)
         return client
@@ -56,10 +70,14 @@ def in_cluster_config() -> Optional[ClusterConfig]:
         return None
     port = os.environ.get("KUBERNETES_SERVICE_PORT", "443")
     ca = SA_DIR / "ca.crt"
+    token = token_file.read_text().strip()
     return ClusterConfig(
         server=f"https://{host}:{port}",
-        token=token_file.read_text().strip(),
+        token=token,
         ca_cert_path=str(ca) if ca.exists() else None,
+        token_file=str(token_file),
+        # bound service-account tokens rotate; the kubelet rewrites the file
+        credential_source=TokenFileSource(str(token_file), initial=token or None),
     )
 
 
@@ -75,6 +93,15 @@ def _materialize(data_b64: Optional[str], path: Optional[str], suffix: str) -> O
     f.write(base64.b64decode(data_b64))
     f.close()
     return f.name
+
+
+def _file_source(path: str, stopgap: Optional[str]) -> TokenFileSource:
+    """Token file configured by hand (kubeconfig ``tokenFile``, --token-file):
+    the file is the credential, so the first ``get()`` reads it; a literal
+    token given next to it only serves while the file cannot be read."""
+    source = TokenFileSource(path, initial=stopgap)
+    source.expire()
+    return source
 
 
 def load_kubeconfig(path: Optional[str] = None, context: Optional[str] = None) -> ClusterConfig:
@@ -103,9 +130,31 @@ def load_kubeconfig(path: Optional[str] = None, context: Optional[str] = None) -
     if not server:
         raise ConfigError(f"cluster {ctx.get('cluster')!r} has no server")
 
+    # credential precedence (client-go): tokenFile, then token, then exec
+    token = user.get("token")
+    token_file = user.get("tokenFile")
+    source: Optional[CredentialSource] = None
+    cfg_dir = os.path.dirname(os.path.abspath(cfg_path))
+    if token_file:
+        if not os.path.isabs(token_file):
+            token_file = os.path.join(cfg_dir, token_file)
+        # a literal token next to tokenFile only bridges the time to the
+        # first successful read, so the first get() goes to the file
+        source = _file_source(token_file, token or None)
+    elif not token and user.get("exec"):
+        source = ExecPluginSource(user["exec"], cluster=cluster, kubeconfig_dir=cfg_dir)
+    if user.get("auth-provider"):
+        log.warning(
+            "kubeconfig user %r uses the legacy auth-provider stanza (%s), which "
+            "is not supported and is ignored; migrate to an exec credential plugin",
+            ctx.get("user"), (user["auth-provider"] or {}).get("name", "unnamed"),
+        )
+
     return ClusterConfig(
         server=server,
-        token=user.get("token"),
+        token=token,
+        token_file=token_file,
+        credential_source=source,
         ca_cert_path=_materialize(
             cluster.get("certificate-authority-data"),
             cluster.get("certificate-authority"),
@@ -122,9 +171,20 @@ def load_kubeconfig(path: Optional[str] = None, context: Optional[str] = None) -
 
 
 def get_config(server: str = "", token: str = "", insecure: bool = False,
-               kubeconfig: Optional[str] = None) -> ClusterConfig:
-    """GetConfigOrDie-style resolution (explicit > in-cluster > kubeconfig)."""
+               kubeconfig: Optional[str] = None,
+               token_file: Optional[str] = None) -> ClusterConfig:
+    """GetConfigOrDie-style resolution (explicit > in-cluster > kubeconfig).
+
+    ``token_file`` goes with an explicit ``server``: the bearer token is read
+    from that file and re-read as it rotates; ``token``, if also given, is
+    used until the first successful read."""
     if server:
+        if token_file:
+            return ClusterConfig(
+                server=server, token=token or None, verify=not insecure,
+                token_file=token_file,
+                credential_source=_file_source(token_file, token or None),
+            )
         return ClusterConfig(server=server, token=token or None, verify=not insecure)
     in_cluster = in_cluster_config()
     if in_cluster is not None:

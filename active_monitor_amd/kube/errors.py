@@ -51,6 +51,19 @@ class ExpiredError(ApiError):
     reason = "Expired"
 
 
+class UnauthorizedError(ApiError):
+    """401: the apiserver refused the credential (after the client's one
+    refresh-and-retry, when it has a credential source)."""
+
+    code = 401
+    reason = "Unauthorized"
+
+
+class ConfigError(Exception):
+    """Cluster connection config or credentials could not be resolved
+    (re-exported by kube/config.py, its historical home)."""
+
+
 def is_not_found(err: Optional[BaseException]) -> bool:
     return isinstance(err, NotFoundError)
 

@@ -19,12 +19,14 @@ from urllib.parse import urlencode, urlsplit
 
 import aiohttp
 
+from .auth import Credential, CredentialSource
 from .errors import (
     AlreadyExistsError,
     ApiError,
     ConflictError,
     InvalidError,
     NotFoundError,
+    UnauthorizedError,
 )
 from .registry import DEFAULT_REGISTRY, Registry
 
@@ -44,6 +46,8 @@ def _error_for(status: int, body: str) -> ApiError:
         pass
     if status == 404:
         return NotFoundError(message)
+    if status == 401:
+        return UnauthorizedError(message)
     if status == 409:
         if reason == "AlreadyExists":
             return AlreadyExistsError(message)
@@ -57,6 +61,11 @@ def _error_for(status: int, body: str) -> ApiError:
 
 class _Expired(Exception):
     """The watch's resourceVersion is too old (HTTP 410 / ERROR event)."""
+
+
+class _WatchUnauthorized(Exception):
+    """The watch connect was refused with 401 and the client has a
+    credential source to ask for a newer credential."""
 
 
 class HttpSubscription:
@@ -88,6 +97,9 @@ class HttpSubscription:
         self._task = asyncio.ensure_future(self._pump())
         #: test/telemetry counter: completed re-list recoveries
         self.relists = 0
+        # a 401 on connect earns one immediate reconnect with a fresh
+        # credential; re-armed by the next connect that is accepted
+        self._auth_retry_armed = True
 
     async def _pump(self) -> None:
         while not self._closed:
@@ -110,6 +122,17 @@ class HttpSubscription:
                 except Exception as e:
                     log.warning("re-list after watch expiry failed: %s", e)
                     await asyncio.sleep(1.0)
+            except _WatchUnauthorized as e:
+                if self._closed:
+                    return
+                if self._auth_retry_armed:
+                    self._auth_retry_armed = False
+                    log.info("watch refused with 401 (%s/%s); reconnecting with "
+                             "a fresh credential", self.api_version, self.kind)
+                    continue
+                log.warning("watch stream error (%s/%s): %s; reconnecting",
+                            self.api_version, self.kind, e)
+                await asyncio.sleep(1.0)
             except Exception as e:
                 if self._closed:
                     return
@@ -142,8 +165,14 @@ class HttpSubscription:
         if self._resource_version:
             params["resourceVersion"] = self._resource_version
         path = self._client._collection_path(self.api_version, self.kind, self.namespace)
+        source = self._client._credentials
+        cred: Optional[Credential] = None
+        headers = None
+        if source is not None:
+            cred = await source.get()
+            headers = {"Authorization": f"Bearer {cred.token}"}
         async with self._client._session.get(
-            self._client.base_url + path, params=params,
+            self._client.base_url + path, params=params, headers=headers,
             # sock_read is the client-side safety net behind the server
             # budget: a connection that goes dead-quiet past it is aborted
             # and the reconnect/resume path takes over
@@ -154,8 +183,12 @@ class HttpSubscription:
             if resp.status == 410:
                 await resp.text()
                 raise _Expired()
+            if resp.status == 401 and source is not None:
+                source.invalidate(cred)
+                raise _WatchUnauthorized(_error_for(401, await resp.text()))
             if resp.status >= 400:
                 raise _error_for(resp.status, await resp.text())
+            self._auth_retry_armed = True
             # incremental framing: newline-delimited JSON without readline's
             # line-length ceiling (a >64 KB Workflow event must not wedge the
             # stream in a reconnect-replay loop)
@@ -360,9 +393,13 @@ class HttpClient:
         registry: Registry = DEFAULT_REGISTRY,
         qps: float = 20.0,
         burst: int = 30,
+        credentials: Optional[CredentialSource] = None,
     ):
         self.base_url = base_url.rstrip("/")
         self.token = token
+        # a credential source supersedes ``token``: the Authorization header
+        # is then resolved per request instead of being fixed in start()
+        self._credentials = credentials
         self.verify = verify
         self.ca_cert = ca_cert
         self.registry = registry
@@ -372,6 +409,9 @@ class HttpClient:
         # plain-HTTP unary fast path (see _ConnPool); None for https targets
         self._pool: Optional[_ConnPool] = None
         self._pool_headers = ""
+        # pool path with a source: the header block rendered for _hdr_cred
+        self._hdr_cred: Optional[Credential] = None
+        self._hdr_block = ""
         # qps<=0 disables throttling (benchmarks measuring the raw wire)
         self._limiter = _TokenBucket(qps, burst)
         #: unary requests issued (observability/bench; watch streams excluded)
@@ -379,7 +419,7 @@ class HttpClient:
 
     async def start(self) -> None:
         headers = {"Content-Type": "application/json"}
-        if self.token:
+        if self.token and self._credentials is None:
             headers["Authorization"] = f"Bearer {self.token}"
         ssl_ctx: Any = None
         if self.base_url.startswith("https"):
@@ -401,7 +441,8 @@ class HttpClient:
             parts = urlsplit(self.base_url)
             self._pool = _ConnPool(parts.hostname or "127.0.0.1", parts.port or 80)
             self._pool_headers = "Content-Type: application/json\r\n" + (
-                f"Authorization: Bearer {self.token}\r\n" if self.token else ""
+                f"Authorization: Bearer {self.token}\r\n"
+                if self.token and self._credentials is None else ""
             )
 
     async def close(self) -> None:
@@ -436,6 +477,10 @@ class HttpClient:
             raise RuntimeError("HttpClient.start() must be called before requests")
         await self._limiter.acquire()
         self.request_count += 1
+        if self._credentials is not None:
+            return await self._with_credentials(
+                lambda cred: self._send(method, path, body, params, cred)
+            )
         if self._pool is not None:
             target = path + ("?" + urlencode(params) if params else "")
             payload = json.dumps(body, separators=(",", ":")).encode() if body is not None else None
@@ -460,6 +505,64 @@ class HttpClient:
             if resp.status >= 400:
                 raise _error_for(resp.status, text)
             return json.loads(text) if text else {}
+
+    # -- requests with a credential source ----------------------------------
+
+    async def _with_credentials(self, send) -> Obj:
+        """Run ``send(credential) -> (status, text)`` with the source's
+        current credential. A 401 means the request was not processed, so for
+        any verb: invalidate what was used, fetch a fresh credential, send
+        once more. The second answer stands, whatever it is."""
+        source = self._credentials
+        cred = await source.get()
+        status, text = await send(cred)
+        if status == 401:
+            source.invalidate(cred)
+            cred = await source.get()
+            await self._limiter.acquire()
+            self.request_count += 1
+            status, text = await send(cred)
+        if status >= 400:
+            raise _error_for(status, text)
+        return json.loads(text) if text else {}
+
+    def _auth_block(self, cred: Credential) -> str:
+        if cred is not self._hdr_cred:
+            self._hdr_block = (
+                f"{self._pool_headers}Authorization: Bearer {cred.token}\r\n"
+            )
+            self._hdr_cred = cred
+        return self._hdr_block
+
+    async def _send(self, method: str, path: str, body: Optional[Obj],
+                    params: Optional[Dict[str, str]],
+                    cred: Credential) -> Tuple[int, str]:
+        if self._pool is not None:
+            target = path + ("?" + urlencode(params) if params else "")
+            payload = json.dumps(body, separators=(",", ":")).encode() if body is not None else None
+            headers = self._auth_block(cred)
+            try:
+                status, text_b = await self._pool.request(method, target, headers, payload)
+            except (ConnectionError, asyncio.IncompleteReadError, OSError):
+                # stale keep-alive connection: one clean retry on a fresh one
+                status, text_b = await self._pool.request(method, target, headers, payload)
+            return status, text_b.decode("utf-8", "replace")
+        async with self._session.request(
+            method, self.base_url + path,
+            json=body if body is not None else None, params=params,
+            headers={"Authorization": f"Bearer {cred.token}"},
+        ) as resp:
+            return resp.status, await resp.text()
+
+    async def _send_patch(self, path: str, patch: Obj,
+                          cred: Optional[Credential]) -> Tuple[int, str]:
+        headers = {"Content-Type": "application/merge-patch+json"}
+        if cred is not None:
+            headers["Authorization"] = f"Bearer {cred.token}"
+        async with self._session.patch(
+            self.base_url + path, data=json.dumps(patch).encode(), headers=headers,
+        ) as resp:
+            return resp.status, await resp.text()
 
     async def get(self, api_version: str, kind: str, namespace: str, name: str,
                   snapshot_read: bool = False) -> Obj:
@@ -515,14 +618,14 @@ class HttpClient:
             path += f"/{subresource}"
         await self._limiter.acquire()
         self.request_count += 1
-        async with self._session.patch(
-            self.base_url + path, data=json.dumps(patch).encode(),
-            headers={"Content-Type": "application/merge-patch+json"},
-        ) as resp:
-            text = await resp.text()
-            if resp.status >= 400:
-                raise _error_for(resp.status, text)
-            return json.loads(text) if text else {}
+        if self._credentials is not None:
+            return await self._with_credentials(
+                lambda cred: self._send_patch(path, patch, cred)
+            )
+        status, text = await self._send_patch(path, patch, None)
+        if status >= 400:
+            raise _error_for(status, text)
+        return json.loads(text) if text else {}
 
     async def delete(self, api_version: str, kind: str, namespace: str, name: str) -> None:
         await self._request("DELETE", self._object_path(api_version, kind, namespace, name))

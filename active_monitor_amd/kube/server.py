@@ -17,18 +17,20 @@ runs against this server.
 from __future__ import annotations
 
 import asyncio
+import hmac
 import json
 import logging
-from typing import Optional, Tuple
+from typing import Optional, Set, Tuple
 from urllib.parse import parse_qsl, unquote, urlsplit
 
-from .errors import ApiError, ExpiredError, InvalidError
+from .errors import ApiError, ExpiredError, InvalidError, UnauthorizedError
 from .memory import MemoryApiServer
 
 log = logging.getLogger("active_monitor_amd.kube.server")
 
 _REASONS = {
-    200: "OK", 201: "Created", 400: "Bad Request", 404: "Not Found",
+    200: "OK", 201: "Created", 400: "Bad Request", 401: "Unauthorized",
+    404: "Not Found",
     405: "Method Not Allowed", 409: "Conflict", 410: "Gone",
     422: "Unprocessable Entity", 500: "Internal Server Error",
 }
@@ -45,11 +47,25 @@ def _status_body(err: ApiError) -> dict:
     }
 
 
+#: served without credentials, as on a real apiserver
+_OPEN_PATHS = frozenset({
+    "/healthz", "/livez", "/readyz", "/version", "/version/",
+})
+
+
 class ApiServerFrontend:
-    def __init__(self, server: MemoryApiServer, host: str = "127.0.0.1", port: int = 0):
+    def __init__(self, server: MemoryApiServer, host: str = "127.0.0.1", port: int = 0,
+                 accepted_tokens: Optional[Set[str]] = None):
         self.server = server
         self.host = host
         self.port = port
+        #: None = open to everyone. A set = bearer-token authn: every request
+        #: but the health probes and /version must carry one of these tokens.
+        #: The set is consulted per request and may be changed while serving
+        #: (that is how tests rotate credentials).
+        self.accepted_tokens = accepted_tokens
+        #: requests answered 401
+        self.unauthorized_count = 0
         self._srv: Optional[asyncio.AbstractServer] = None
         self._live_subs: list = []
 
@@ -78,6 +94,34 @@ class ApiServerFrontend:
         for sub in list(self._live_subs):
             sub.close()
 
+    # -- authn --------------------------------------------------------------
+
+    def _authorized(self, path: str, authorization: bytes) -> bool:
+        if path in _OPEN_PATHS:
+            return True
+        ok = False
+        scheme, _, presented = authorization.partition(b" ")
+        if scheme.lower() == b"bearer":
+            presented = presented.strip()
+            # every candidate is compared, in constant time each
+            for tok in list(self.accepted_tokens or ()):
+                if hmac.compare_digest(presented, tok.encode("utf-8")):
+                    ok = True
+        if not ok:
+            self.unauthorized_count += 1
+        return ok
+
+    @staticmethod
+    def _unauthorized_response() -> bytes:
+        payload = json.dumps(
+            _status_body(UnauthorizedError("Unauthorized")), separators=(",", ":")
+        ).encode()
+        return (
+            f"HTTP/1.1 401 Unauthorized\r\nContent-Type: application/json\r\n"
+            f"WWW-Authenticate: Bearer\r\n"
+            f"Content-Length: {len(payload)}\r\n\r\n"
+        ).encode("latin-1") + payload
+
     # -- HTTP protocol ------------------------------------------------------
 
     async def _handle_conn(self, reader: asyncio.StreamReader,
@@ -95,6 +139,7 @@ class ApiServerFrontend:
                 content_type = ""
                 expect_continue = False
                 want_table = False
+                authorization = b""
                 while True:
                     line = await reader.readline()
                     if line in (b"\r\n", b"\n", b""):
@@ -108,6 +153,8 @@ class ApiServerFrontend:
                         expect_continue = True  # curl sends this for big bodies
                     elif lower.startswith(b"accept:") and b"as=table" in lower:
                         want_table = True
+                    elif lower.startswith(b"authorization:"):
+                        authorization = line.split(b":", 1)[1].strip()
                 if expect_continue:
                     writer.write(b"HTTP/1.1 100 Continue\r\n\r\n")
                     await writer.drain()
@@ -117,6 +164,12 @@ class ApiServerFrontend:
                 path = unquote(parts.path)
                 query = dict(parse_qsl(parts.query))
 
+                if (self.accepted_tokens is not None
+                        and not self._authorized(path, authorization)):
+                    # the body was consumed above, so keep-alive survives
+                    writer.write(self._unauthorized_response())
+                    await writer.drain()
+                    continue
                 if query.get("watch") in ("true", "1"):
                     await self._serve_watch(writer, path, query)
                     return  # watch streams own the connection

@@ -65,14 +65,31 @@ def parse_args(argv=None):
     p.add_argument("--engine-ttl", type=float, default=60.0,
                    help="completed-workflow TTL seconds (Argo ttlStrategy "
                         "equivalent; bounds server memory at fleet rates)")
+    p.add_argument("--token-file", default=None, metavar="FILE",
+                   help="require 'Authorization: Bearer <token>' on every "
+                        "request but the health probes and /version; FILE "
+                        "holds one accepted token per line, read at start "
+                        "(default: no authentication)")
     return p.parse_args(argv)
+
+
+def read_accepted_tokens(path: str) -> set:
+    with open(path, "r") as f:
+        tokens = {line.strip() for line in f if line.strip()}
+    if not tokens:
+        raise SystemExit(f"--token-file {path}: no tokens in file")
+    return tokens
 
 
 async def amain(args) -> int:
     from .client import MemoryClient
 
     server = MemoryApiServer()
-    frontend = ApiServerFrontend(server, args.host, args.port)
+    accepted = None
+    if getattr(args, "token_file", None):
+        accepted = read_accepted_tokens(args.token_file)
+    frontend = ApiServerFrontend(server, args.host, args.port,
+                                 accepted_tokens=accepted)
     await frontend.start()
 
     engine = None
