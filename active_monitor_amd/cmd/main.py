@@ -78,6 +78,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--serve-api", default="",
                    help="memory backend: also serve the store over the "
                         "Kubernetes REST API at this address (kubectl-able)")
+    p.add_argument("--data-dir", default=None, metavar="DIR",
+                   help="memory backend: keep the store in DIR (snapshot + "
+                        "journal) so HealthChecks, counters and workflows "
+                        "survive a restart; one process per directory")
     p.add_argument("--shard-index", type=int, default=0,
                    help="this controller's shard (keyspace split by CR-name hash)")
     p.add_argument("--shard-count", type=int, default=1,
@@ -151,11 +155,25 @@ async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
             await client.close()
             return 1
     else:
-        client = MemoryClient(MemoryApiServer())
+        data_dir = getattr(args, "data_dir", None)
+        if data_dir:
+            from ..kube.persist import StoreError
+
+            try:
+                store = MemoryApiServer.open(data_dir)
+            except (StoreError, OSError) as e:
+                log.error("cannot open data directory: %s", e)
+                return 1
+            log.info("data directory %s: loaded %d objects, resourceVersion %s",
+                     store.data_dir, len(store), store.resource_version())
+        else:
+            store = MemoryApiServer()
+        client = MemoryClient(store)
         if args.workflow_engine == "local":
             from ..workflow import LocalWorkflowEngine
 
-            engine = LocalWorkflowEngine(client, args.namespace)
+            engine = LocalWorkflowEngine(client, args.namespace,
+                                         recover=bool(data_dir))
         if args.serve_api:
             from ..kube.server import ApiServerFrontend
 
@@ -226,11 +244,16 @@ async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         await client.close()
     if args.backend == "memory" and args.serve_api:
         await frontend.stop()
+    if args.backend == "memory":
+        client.server.close()
     return rc
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.data_dir and args.backend != "memory":
+        parser.error("--data-dir applies to --backend memory only")
     try:
         return asyncio.run(run(args))
     except KeyboardInterrupt:

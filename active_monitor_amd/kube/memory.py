@@ -17,6 +17,10 @@ exercises:
 
 The core is synchronous and thread-safe; watches are asyncio queues fed via
 ``call_soon_threadsafe`` so any thread may mutate the store.
+
+``MemoryApiServer()`` lives and dies with the process.
+``MemoryApiServer.open(data_dir)`` is the same store journaled to a directory
+(:mod:`.persist`), for standalone deployments that must survive a restart.
 """
 from __future__ import annotations
 
@@ -188,6 +192,67 @@ class MemoryApiServer:
         # highest rv evicted from history — the compaction horizon; resuming
         # below it is 410 Gone
         self._compacted_rv = 0
+        # on-disk journal (kube/persist.py); None unless opened with open()
+        self._journal = None
+
+    @classmethod
+    def open(cls, data_dir: str, registry: Registry = DEFAULT_REGISTRY,
+             sync_interval: float = 1.0,
+             compact_threshold: int = 4096) -> "MemoryApiServer":
+        """A store that survives the process: state is loaded from
+        ``data_dir`` (created if missing) and every mutation is journaled
+        there before it becomes visible. A kill of the process loses nothing
+        acknowledged; a power loss can lose up to ``sync_interval`` seconds.
+        The journal is folded into the snapshot once it holds more than
+        ``compact_threshold`` records (and more than there are live objects).
+
+        Raises :class:`~.persist.StoreLockedError` when another process holds
+        the directory and :class:`~.persist.StoreCorruptError` when it cannot
+        be read. Call :meth:`close` when done.
+
+        An I/O error while journaling is raised from the mutating call; by
+        then the mutation is applied in memory (visible to ``get``/``list``,
+        to no watcher) but not on disk, and every later write raises
+        :class:`~.persist.StoreError`. Restart the process: it reloads the
+        last journaled state.
+
+        The Event cap restarts from the live Events in creation order. A
+        running store also counts Events that were deleted or cascaded away
+        since (their keys stay queued until evicted), so it may start
+        evicting a little earlier than the same store after a reload.
+
+        The watch history restarts empty with the compaction horizon at the
+        restored resourceVersion: a watch resuming from before the restart
+        gets 410 Gone and re-lists, one resuming exactly there is valid."""
+        from .persist import Journal
+
+        self = cls(registry)
+        journal = Journal(data_dir, sync_interval, compact_threshold)
+        try:
+            rv, objects = journal.load(self._key)
+        except BaseException:
+            journal.close()
+            raise
+        self._objects = objects
+        for key, obj in objects.items():
+            self._index_owners(key, obj)
+            # dict order is creation order per key: a put keeps its place
+            if key[1] == "Event":
+                self._event_keys.append(key)
+        self._rv = self._compacted_rv = rv
+        self._journal = journal
+        return self
+
+    @property
+    def data_dir(self) -> Optional[str]:
+        return None if self._journal is None else self._journal.data_dir
+
+    def close(self) -> None:
+        """Flush, sync and release the data directory (idempotent; a no-op
+        for a store without one). The store must not be written afterwards."""
+        with self._lock:
+            if self._journal is not None and not self._journal.closed:
+                self._journal.close()
 
     # -- internals ---------------------------------------------------------
 
@@ -229,11 +294,27 @@ class MemoryApiServer:
             rv = int((obj.get("metadata") or {}).get("resourceVersion", 0))
         except (TypeError, ValueError):
             rv = self._rv
+        if self._journal is not None:
+            self._journal_event(ev_type, obj, rv)
         self._history.append((rv, ev_type, obj))
         while len(self._history) > self.history_window:
             self._compacted_rv = self._history.popleft()[0]
         for sub in list(self._subs):
             sub._offer(event)
+
+    def _journal_event(self, ev_type: str, obj: Obj, rv: int) -> None:
+        """Write-ahead of visibility: the record is in the OS before the
+        event reaches the history or any watcher. Serialised here, under the
+        store lock, because ``obj`` shares subtrees with the live object."""
+        journal = self._journal
+        if ev_type == "DELETED":
+            journal.delete(rv, self._key(obj))
+        else:
+            journal.put(rv, obj)
+        # every caller has brought _objects up to this event already, so the
+        # store is exactly the journal replayed up to here
+        if journal.should_compact(len(self._objects)):
+            journal.compact(self._rv, self._objects.values(), len(self._objects))
 
     def events_since(self, api_version: str, kind: str, namespace: Optional[str],
                      resource_version: str) -> List[Dict[str, Any]]:
@@ -311,6 +392,10 @@ class MemoryApiServer:
                     dropped = self._objects.pop(old, None)
                     if dropped is not None:
                         self._unindex_owners(old, dropped)
+                        if self._journal is not None:
+                            # cap evictions publish no event; they share
+                            # the rv of the create that caused them
+                            self._journal.delete(self._rv, old)
             out = snapshot(obj)
             self._publish("ADDED", out)
             if not transfer:

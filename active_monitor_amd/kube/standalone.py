@@ -70,6 +70,10 @@ def parse_args(argv=None):
                         "request but the health probes and /version; FILE "
                         "holds one accepted token per line, read at start "
                         "(default: no authentication)")
+    p.add_argument("--data-dir", default=None, metavar="DIR",
+                   help="keep the store in DIR (snapshot + journal) so a "
+                        "restart finds every object again; one process per "
+                        "directory (default: memory only)")
     return p.parse_args(argv)
 
 
@@ -81,10 +85,33 @@ def read_accepted_tokens(path: str) -> set:
     return tokens
 
 
+def open_durable_store(data_dir: str):
+    """Open the store kept in ``data_dir`` and say what was found; on a
+    locked or unreadable directory print the reason and return None — the
+    caller exits 1 and never starts an empty store over it."""
+    from .persist import StoreError
+
+    try:
+        server = MemoryApiServer.open(data_dir)
+    except (StoreError, OSError) as e:
+        print(f"cannot open data directory: {e}", file=sys.stderr, flush=True)
+        return None
+    print(f"data directory {server.data_dir}: loaded {len(server)} objects, "
+          f"resourceVersion {server.resource_version()}",
+          file=sys.stderr, flush=True)
+    return server
+
+
 async def amain(args) -> int:
     from .client import MemoryClient
 
-    server = MemoryApiServer()
+    data_dir = getattr(args, "data_dir", None)
+    if data_dir:
+        server = open_durable_store(data_dir)
+        if server is None:
+            return 1
+    else:
+        server = MemoryApiServer()
     accepted = None
     if getattr(args, "token_file", None):
         accepted = read_accepted_tokens(args.token_file)
@@ -101,11 +128,13 @@ async def amain(args) -> int:
             policy=bench_policy(args.remedy_frac),
             delay=args.engine_delay,
             ttl_seconds=args.engine_ttl,
+            recover=bool(data_dir),
         )
     elif args.engine == "local":
         from ..workflow import LocalWorkflowEngine
 
-        engine = LocalWorkflowEngine(MemoryClient(server), ttl_seconds=args.engine_ttl)
+        engine = LocalWorkflowEngine(MemoryClient(server), ttl_seconds=args.engine_ttl,
+                                     recover=bool(data_dir))
     if engine is not None:
         await engine.start()
 
@@ -124,6 +153,7 @@ async def amain(args) -> int:
     if engine is not None:
         await engine.stop()
     await frontend.stop()
+    server.close()
     return 0
 
 

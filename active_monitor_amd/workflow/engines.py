@@ -54,15 +54,30 @@ class _EngineBase:
     """``ttl_seconds`` deletes completed workflows after the given delay —
     the role Argo's ``ttlStrategy.secondsAfterCompletion`` plays for the
     reference (its install configures 1800s, deploy-argo.yaml:1162-1173);
-    None disables (tests that inspect completed workflows)."""
+    None disables (tests that inspect completed workflows).
+
+    ``recover=True`` is for a store that outlives the engine (a durable
+    data directory): ``start()`` also lists the Workflows that are already
+    there. One that was never picked up runs as if just added; one left
+    ``Running`` by a previous process is failed, never re-run (a remedy is
+    not idempotent and a half-run DAG cannot be resumed); one already
+    terminal gets its lost TTL timer re-armed for the time it has left."""
 
     DEFAULT_TTL = 1800.0
+    INTERRUPTED_MESSAGE = "workflow interrupted: engine restarted"
 
     def __init__(self, client: KubeClient, namespace: Optional[str] = None,
-                 ttl_seconds: Optional[float] = DEFAULT_TTL):
+                 ttl_seconds: Optional[float] = DEFAULT_TTL,
+                 recover: bool = False):
         self.client = client
         self.namespace = namespace
         self.ttl_seconds = ttl_seconds
+        self.recover = recover
+        # uids taken from the start-up list; their ADDED event, should the
+        # watch deliver one as well, is dropped. Emptied by the first event
+        # newer than everything in that list (_recovered_rv).
+        self._recovered: set = set()
+        self._recovered_rv = 0
         self._task: Optional[asyncio.Task] = None
         self._sub = None
         self._inflight: Dict[str, asyncio.Task] = {}
@@ -72,6 +87,16 @@ class _EngineBase:
 
     async def start(self) -> None:
         self._sub = self.client.watch(WF_API_VERSION, WF_KIND, self.namespace)
+        if self.recover:
+            # watch first, then list: nothing created in between is missed
+            finished = []
+            for wf in await self.client.list(WF_API_VERSION, WF_KIND, self.namespace):
+                self._recover(wf, finished)
+            # shortest remaining TTL first, so that _ttl_handles stays in
+            # firing order
+            finished.sort(key=lambda pair: pair[0])
+            for left, wf in finished:
+                self._schedule_ttl(wf, left)
         self._task = asyncio.ensure_future(self._loop())
 
     async def stop(self) -> None:
@@ -91,22 +116,95 @@ class _EngineBase:
 
     async def _loop(self) -> None:
         async for ev in self._sub:
+            wf = ev["object"]
+            if self._recovered and self._taken_at_start(ev["type"], wf):
+                continue
             if ev["type"] != "ADDED":
                 continue
-            wf = ev["object"]
             if (wf.get("status") or {}).get("phase") in ("Succeeded", "Failed"):
                 continue
-            key = f'{(wf["metadata"].get("namespace", ""))}/{wf["metadata"]["name"]}'
-            task = asyncio.ensure_future(self._run(wf))
-            self._inflight[key] = task
-            task.add_done_callback(lambda t, k=key: self._inflight.pop(k, None))
+            self._spawn(wf, self._run(wf))
+
+    def _taken_at_start(self, ev_type: str, wf: Dict[str, Any]) -> bool:
+        """True for the ADDED event of a workflow that the start-up list
+        already handed to :meth:`_recover`. Events arrive in resourceVersion
+        order, so the first one newer than everything in that list ends the
+        overlap and the set is dropped."""
+        meta = wf["metadata"]
+        try:
+            if int(meta.get("resourceVersion")) > self._recovered_rv:
+                self._recovered.clear()
+                return False
+        except (TypeError, ValueError):
+            pass  # opaque resourceVersion: keep matching by uid
+        return ev_type == "ADDED" and meta.get("uid") in self._recovered
+
+    def _spawn(self, wf: Dict[str, Any], coro: Any) -> None:
+        key = f'{(wf["metadata"].get("namespace", ""))}/{wf["metadata"]["name"]}'
+        task = asyncio.ensure_future(coro)
+        self._inflight[key] = task
+        task.add_done_callback(lambda t, k=key: self._inflight.pop(k, None))
+
+    def _recover(self, wf: Dict[str, Any], finished: List[Any]) -> None:
+        """Handle one Workflow found at start by the state it is in; a
+        terminal one is appended to ``finished`` as ``(ttl left, wf)`` for
+        the caller to schedule."""
+        meta = wf["metadata"]
+        key = f'{meta.get("namespace", "")}/{meta["name"]}'
+        if key in self._inflight:
+            return
+        status = wf.get("status") or {}
+        phase = status.get("phase")
+        if phase in ("Succeeded", "Failed", "Error"):
+            if self.ttl_seconds is not None:
+                finished.append((self._ttl_left(status.get("finishedAt")), wf))
+            return
+        if phase and phase != "Running":
+            return  # a phase no local engine writes: not ours to touch
+        if meta.get("uid"):
+            self._recovered.add(meta["uid"])
+            try:
+                self._recovered_rv = max(self._recovered_rv,
+                                         int(meta.get("resourceVersion")))
+            except (TypeError, ValueError):
+                pass
+        if not phase:
+            log.info("recovering pending workflow %s", key)
+            self._spawn(wf, self._run(wf))
+        else:
+            log.warning("workflow %s was running when the engine stopped: "
+                        "failing it", key)
+            self._spawn(wf, self._fail_interrupted(wf))
+
+    def _ttl_left(self, finished_at: Any) -> float:
+        """``ttl_seconds`` less the time since ``finishedAt``, floored at 0;
+        a missing or unparsable ``finishedAt`` counts from now."""
+        from ..api.types import parse_k8s_time
+
+        try:
+            finished = parse_k8s_time(finished_at)
+        except (TypeError, ValueError):
+            finished = None
+        if finished is None:
+            return self.ttl_seconds
+        age = max(time.time() - finished.timestamp(), 0.0)
+        return max(self.ttl_seconds - age, 0.0)
+
+    async def _fail_interrupted(self, wf: Dict[str, Any]) -> None:
+        status = dict(wf.get("status") or {})
+        status.update(phase="Failed", finishedAt=_now_iso(),
+                      message=self.INTERRUPTED_MESSAGE)
+        await self._set_status(wf, status)
+        self._schedule_ttl(wf)
 
     async def _run(self, wf: Dict[str, Any]) -> None:  # pragma: no cover - abstract
         raise NotImplementedError
 
-    def _schedule_ttl(self, wf: Dict[str, Any]) -> None:
+    def _schedule_ttl(self, wf: Dict[str, Any], delay: Optional[float] = None) -> None:
         if self.ttl_seconds is None:
             return
+        if delay is None:
+            delay = self.ttl_seconds
         meta = wf["metadata"]
         ns, name = meta.get("namespace", ""), meta["name"]
 
@@ -124,9 +222,11 @@ class _EngineBase:
             )
 
         loop = asyncio.get_event_loop()
-        self._ttl_handles.append(loop.call_later(self.ttl_seconds, _gc))
-        # handles are appended in firing order (constant ttl): drop spent
-        # ones from the front — O(1) amortized
+        self._ttl_handles.append(loop.call_later(delay, _gc))
+        # handles are appended in firing order (constant ttl; start() arms
+        # the remaining TTLs of recovered workflows first, shortest first,
+        # and none exceeds ttl): drop spent ones from the front — O(1)
+        # amortized
         now = loop.time()
         while self._ttl_handles and (
             self._ttl_handles[0].cancelled() or self._ttl_handles[0].when() <= now
@@ -160,8 +260,9 @@ class ScriptedWorkflowEngine(_EngineBase):
         delay: float = 0.0,
         namespace: Optional[str] = None,
         ttl_seconds: Optional[float] = _EngineBase.DEFAULT_TTL,
+        recover: bool = False,
     ):
-        super().__init__(client, namespace, ttl_seconds)
+        super().__init__(client, namespace, ttl_seconds, recover)
         self.policy = policy
         self.delay = delay
         self.completed = 0
@@ -226,8 +327,9 @@ class LocalWorkflowEngine(_EngineBase):
     """
 
     def __init__(self, client: KubeClient, namespace: Optional[str] = None,
-                 ttl_seconds: Optional[float] = _EngineBase.DEFAULT_TTL):
-        super().__init__(client, namespace, ttl_seconds)
+                 ttl_seconds: Optional[float] = _EngineBase.DEFAULT_TTL,
+                 recover: bool = False):
+        super().__init__(client, namespace, ttl_seconds, recover)
         self.completed = 0
 
     async def stop(self) -> None:
