@@ -2,7 +2,7 @@
 # targets, adapted to the Python stack).
 PY ?= python3
 
-.PHONY: test test-gpu bench run manifests native docker-build sweep soak e2e-kind lint
+.PHONY: test test-gpu bench run manifests native native-check docker-build sweep soak e2e-kind lint
 
 test:
 	$(PY) -m pytest tests/ -q -m "not gpu"
@@ -21,6 +21,24 @@ run:
 
 native:
 	$(PY) setup.py build_ext --inplace
+
+# Memory-safety check of the C code, CPU only: two stand-alone programs built
+# with the sanitizers (native/check/). check_head links the Python-free head
+# parsers; check_json is an interpreter with the extension compiled in, run
+# on the JSON corpus of tests/unit/test_wirecodec_json.py. The extension is
+# never loaded under a sanitizer from inside `python`.
+SANITIZE = -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	-fno-omit-frame-pointer -g -O1 -Wall -Wextra -Inative
+
+native-check:
+	$(CC) $(SANITIZE) -o native/check/check_head \
+		native/check/check_head.c native/wirehead.c
+	native/check/check_head
+	$(CC) $(SANITIZE) -Wno-unused-parameter $$($(PY)-config --includes) \
+		-o native/check/check_json native/check/check_json.c \
+		native/_amcore.c native/wirejson.c native/wirehead.c \
+		$$($(PY)-config --embed --ldflags)
+	ASAN_OPTIONS=detect_leaks=0 native/check/check_json native/check/check_json.py
 
 manifests:
 	$(PY) -m active_monitor_amd.api.crd > config/crd/bases/activemonitor.keikoproj.io_healthchecks.yaml

@@ -14,11 +14,12 @@ import logging
 import ssl
 import time
 from collections import deque
-from typing import Any, AsyncIterator, Dict, List, Optional, Tuple
+from typing import Any, AsyncIterator, Dict, List, Optional, Tuple, Union
 from urllib.parse import urlencode, urlsplit
 
 import aiohttp
 
+from ..utils import wirecodec
 from .auth import Credential, CredentialSource
 from .errors import (
     AlreadyExistsError,
@@ -57,6 +58,19 @@ def _error_for(status: int, body: str) -> ApiError:
     err = ApiError(message)
     err.code = status
     return err
+
+
+def _as_text(raw: Union[bytes, str]) -> str:
+    """Response body as text: the pool hands over bytes, aiohttp text."""
+    return raw.decode("utf-8", "replace") if isinstance(raw, bytes) else raw
+
+
+def _decode_body(raw: Union[bytes, str]) -> Obj:
+    if not raw:
+        return {}
+    if isinstance(raw, bytes):
+        return wirecodec.loads_lenient(raw)
+    return json.loads(raw)
 
 
 class _Expired(Exception):
@@ -206,7 +220,7 @@ class HttpSubscription:
                     del buf[: nl + 1]
                     if not line:
                         continue
-                    self._handle_event(json.loads(line))
+                    self._handle_event(wirecodec.loads_strict(line))
                     if self._closed:
                         return
 
@@ -322,35 +336,39 @@ class _ConnPool:
 
     async def request(self, method: str, target: str, headers: str,
                       body: Optional[bytes]) -> Tuple[int, bytes]:
+        head = (
+            f"{method} {target} HTTP/1.1\r\nHost: {self.host}:{self.port}\r\n"
+            f"{headers}Content-Length: {len(body) if body else 0}\r\n\r\n"
+        ).encode("latin-1")
+        return await self._roundtrip(head + body if body else head)
+
+    async def request_json(self, method: str, target: str, headers: str,
+                           obj: Optional[Obj]) -> Tuple[int, bytes]:
+        """``request`` with a JSON body (None: no body), head and payload
+        framed into one buffer by the wire codec."""
+        prefix = (
+            f"{method} {target} HTTP/1.1\r\nHost: {self.host}:{self.port}\r\n"
+            f"{headers}"
+        ).encode("latin-1")
+        return await self._roundtrip(wirecodec.frame(prefix, obj))
+
+    async def _roundtrip(self, data: bytes) -> Tuple[int, bytes]:
         conn = await self._acquire()
         reader, writer = conn
         ok = False
         try:
-            head = (
-                f"{method} {target} HTTP/1.1\r\nHost: {self.host}:{self.port}\r\n"
-                f"{headers}Content-Length: {len(body) if body else 0}\r\n\r\n"
-            ).encode("latin-1")
-            writer.write(head + body if body else head)
+            writer.write(data)
             await writer.drain()
 
-            status_line = await reader.readline()
-            if not status_line:
-                raise ConnectionResetError("server closed connection")
-            status = int(status_line.split(b" ", 2)[1])
-            content_length = 0
-            chunked = False
-            keep_alive = True
-            while True:
-                line = await reader.readline()
-                if line in (b"\r\n", b"\n", b""):
-                    break
-                lower = line.lower()
-                if lower.startswith(b"content-length:"):
-                    content_length = int(line.split(b":", 1)[1])
-                elif lower.startswith(b"transfer-encoding:") and b"chunked" in lower:
-                    chunked = True
-                elif lower.startswith(b"connection:") and b"close" in lower:
-                    keep_alive = False
+            try:
+                head = await reader.readuntil(b"\r\n\r\n")
+            except asyncio.IncompleteReadError as e:
+                if not e.partial:
+                    raise ConnectionResetError("server closed connection") from None
+                raise
+            status, content_length, chunked, keep_alive = (
+                wirecodec.parse_response_head(head)
+            )
             if chunked:
                 chunks = []
                 while True:
@@ -483,20 +501,18 @@ class HttpClient:
             )
         if self._pool is not None:
             target = path + ("?" + urlencode(params) if params else "")
-            payload = json.dumps(body, separators=(",", ":")).encode() if body is not None else None
             try:
-                status, text_b = await self._pool.request(
-                    method, target, self._pool_headers, payload
+                status, text_b = await self._pool.request_json(
+                    method, target, self._pool_headers, body
                 )
             except (ConnectionError, asyncio.IncompleteReadError, OSError):
                 # stale keep-alive connection: one clean retry on a fresh one
-                status, text_b = await self._pool.request(
-                    method, target, self._pool_headers, payload
+                status, text_b = await self._pool.request_json(
+                    method, target, self._pool_headers, body
                 )
-            text = text_b.decode("utf-8", "replace")
-            if status >= 400:
-                raise _error_for(status, text)
-            return json.loads(text) if text else {}
+            if status >= 400:  # only the error path needs text
+                raise _error_for(status, text_b.decode("utf-8", "replace"))
+            return wirecodec.loads_lenient(text_b) if text_b else {}
         async with self._session.request(
             method, self.base_url + path,
             json=body if body is not None else None, params=params,
@@ -515,16 +531,16 @@ class HttpClient:
         once more. The second answer stands, whatever it is."""
         source = self._credentials
         cred = await source.get()
-        status, text = await send(cred)
+        status, raw = await send(cred)
         if status == 401:
             source.invalidate(cred)
             cred = await source.get()
             await self._limiter.acquire()
             self.request_count += 1
-            status, text = await send(cred)
+            status, raw = await send(cred)
         if status >= 400:
-            raise _error_for(status, text)
-        return json.loads(text) if text else {}
+            raise _error_for(status, _as_text(raw))
+        return _decode_body(raw)
 
     def _auth_block(self, cred: Credential) -> str:
         if cred is not self._hdr_cred:
@@ -536,17 +552,15 @@ class HttpClient:
 
     async def _send(self, method: str, path: str, body: Optional[Obj],
                     params: Optional[Dict[str, str]],
-                    cred: Credential) -> Tuple[int, str]:
+                    cred: Credential) -> Tuple[int, Union[bytes, str]]:
         if self._pool is not None:
             target = path + ("?" + urlencode(params) if params else "")
-            payload = json.dumps(body, separators=(",", ":")).encode() if body is not None else None
             headers = self._auth_block(cred)
             try:
-                status, text_b = await self._pool.request(method, target, headers, payload)
+                return await self._pool.request_json(method, target, headers, body)
             except (ConnectionError, asyncio.IncompleteReadError, OSError):
                 # stale keep-alive connection: one clean retry on a fresh one
-                status, text_b = await self._pool.request(method, target, headers, payload)
-            return status, text_b.decode("utf-8", "replace")
+                return await self._pool.request_json(method, target, headers, body)
         async with self._session.request(
             method, self.base_url + path,
             json=body if body is not None else None, params=params,
@@ -560,7 +574,7 @@ class HttpClient:
         if cred is not None:
             headers["Authorization"] = f"Bearer {cred.token}"
         async with self._session.patch(
-            self.base_url + path, data=json.dumps(patch).encode(), headers=headers,
+            self.base_url + path, data=wirecodec.dumpb(patch), headers=headers,
         ) as resp:
             return resp.status, await resp.text()
 

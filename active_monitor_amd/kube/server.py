@@ -18,11 +18,11 @@ from __future__ import annotations
 
 import asyncio
 import hmac
-import json
 import logging
 from typing import Optional, Set, Tuple
-from urllib.parse import parse_qsl, unquote, urlsplit
 
+from ..utils import wirecodec
+from ..utils.wirecodec import EXPECT_CONTINUE, WANT_TABLE
 from .errors import ApiError, ExpiredError, InvalidError, UnauthorizedError
 from .memory import MemoryApiServer
 
@@ -34,6 +34,29 @@ _REASONS = {
     405: "Method Not Allowed", 409: "Conflict", 410: "Gone",
     422: "Unprocessable Entity", 500: "Internal Server Error",
 }
+
+
+#: status line + Content-Type of a JSON response, per status code; the
+#: Content-Length line and the payload are appended by wirecodec.frame
+_JSON_PREFIX = {
+    code: (f"HTTP/1.1 {code} {reason}\r\n"
+           f"Content-Type: application/json\r\n").encode("latin-1")
+    for code, reason in _REASONS.items()
+}
+_UNAUTHORIZED_PREFIX = (
+    b"HTTP/1.1 401 Unauthorized\r\nContent-Type: application/json\r\n"
+    b"WWW-Authenticate: Bearer\r\n"
+)
+
+
+def _json_prefix(status: int) -> bytes:
+    prefix = _JSON_PREFIX.get(status)
+    if prefix is None:  # a code without a reason phrase of its own
+        prefix = _JSON_PREFIX[status] = (
+            f"HTTP/1.1 {status} OK\r\n"
+            f"Content-Type: application/json\r\n"
+        ).encode("latin-1")
+    return prefix
 
 
 def _status_body(err: ApiError) -> dict:
@@ -113,14 +136,9 @@ class ApiServerFrontend:
 
     @staticmethod
     def _unauthorized_response() -> bytes:
-        payload = json.dumps(
-            _status_body(UnauthorizedError("Unauthorized")), separators=(",", ":")
-        ).encode()
-        return (
-            f"HTTP/1.1 401 Unauthorized\r\nContent-Type: application/json\r\n"
-            f"WWW-Authenticate: Bearer\r\n"
-            f"Content-Length: {len(payload)}\r\n\r\n"
-        ).encode("latin-1") + payload
+        return wirecodec.frame(
+            _UNAUTHORIZED_PREFIX, _status_body(UnauthorizedError("Unauthorized"))
+        )
 
     # -- HTTP protocol ------------------------------------------------------
 
@@ -128,41 +146,18 @@ class ApiServerFrontend:
                            writer: asyncio.StreamWriter) -> None:
         try:
             while True:
-                request_line = await reader.readline()
-                if not request_line or request_line in (b"\r\n", b"\n"):
+                # one read for the whole head (it ends at CRLF CRLF) and one
+                # parse of it: utils/wirecodec.py
+                head = await reader.readuntil(b"\r\n\r\n")
+                parsed = wirecodec.parse_request_head(head)
+                if parsed is None:
                     return
-                try:
-                    method, target, _ = request_line.decode("latin-1").split(" ", 2)
-                except ValueError:
-                    return
-                content_length = 0
-                content_type = ""
-                expect_continue = False
-                want_table = False
-                authorization = b""
-                while True:
-                    line = await reader.readline()
-                    if line in (b"\r\n", b"\n", b""):
-                        break
-                    lower = line.lower()
-                    if lower.startswith(b"content-length:"):
-                        content_length = int(line.split(b":", 1)[1])
-                    elif lower.startswith(b"content-type:"):
-                        content_type = line.split(b":", 1)[1].strip().decode("latin-1")
-                    elif lower.startswith(b"expect:") and b"100-continue" in lower:
-                        expect_continue = True  # curl sends this for big bodies
-                    elif lower.startswith(b"accept:") and b"as=table" in lower:
-                        want_table = True
-                    elif lower.startswith(b"authorization:"):
-                        authorization = line.split(b":", 1)[1].strip()
-                if expect_continue:
+                (method, path, query, content_length, content_type, flags,
+                 authorization) = parsed
+                if flags & EXPECT_CONTINUE:
                     writer.write(b"HTTP/1.1 100 Continue\r\n\r\n")
                     await writer.drain()
                 body = await reader.readexactly(content_length) if content_length else b""
-
-                parts = urlsplit(target)
-                path = unquote(parts.path)
-                query = dict(parse_qsl(parts.query))
 
                 if (self.accepted_tokens is not None
                         and not self._authorized(path, authorization)):
@@ -175,23 +170,24 @@ class ApiServerFrontend:
                     return  # watch streams own the connection
                 status, obj = self._serve_unary(method, path, query, body,
                                                 content_type)
-                if (want_table and method == "GET" and status == 200
+                if (flags & WANT_TABLE and method == "GET" and status == 200
                         and isinstance(obj, dict)):
                     obj = self._to_table(obj)
                 if isinstance(obj, str):  # health probes are plain text
-                    payload, ctype = obj.encode(), "text/plain"
+                    payload = obj.encode()
+                    writer.write(
+                        (
+                            f"HTTP/1.1 {status} {_REASONS.get(status, 'OK')}\r\n"
+                            f"Content-Type: text/plain\r\n"
+                            f"Content-Length: {len(payload)}\r\n\r\n"
+                        ).encode("latin-1") + payload
+                    )
                 else:
-                    payload = json.dumps(obj, separators=(",", ":")).encode() if obj is not None else b""
-                    ctype = "application/json"
-                writer.write(
-                    (
-                        f"HTTP/1.1 {status} {_REASONS.get(status, 'OK')}\r\n"
-                        f"Content-Type: {ctype}\r\n"
-                        f"Content-Length: {len(payload)}\r\n\r\n"
-                    ).encode("latin-1") + payload
-                )
+                    writer.write(wirecodec.frame(_json_prefix(status), obj))
                 await writer.drain()
-        except (ConnectionError, asyncio.IncompleteReadError, asyncio.CancelledError):
+        except (ConnectionError, asyncio.IncompleteReadError,
+                asyncio.LimitOverrunError, asyncio.CancelledError):
+            # LimitOverrunError: a head longer than the reader's limit
             pass
         except Exception:  # defensive: never kill the accept loop
             log.exception("frontend connection handler failed")
@@ -377,7 +373,7 @@ class ApiServerFrontend:
     @staticmethod
     def _parse_body(body: bytes) -> dict:
         try:
-            obj = json.loads(body)
+            obj = wirecodec.loads_strict(body)
             if not isinstance(obj, dict):
                 raise ValueError
             return obj
@@ -481,11 +477,7 @@ class ApiServerFrontend:
             except KeyError:
                 err = ApiError(f"unknown resource {tail}")
         if err is not None:
-            payload = json.dumps(_status_body(err), separators=(",", ":")).encode()
-            writer.write(
-                (f"HTTP/1.1 404 Not Found\r\nContent-Type: application/json\r\n"
-                 f"Content-Length: {len(payload)}\r\n\r\n").encode() + payload
-            )
+            writer.write(wirecodec.frame(_json_prefix(404), _status_body(err)))
             await writer.drain()
             return
         kind = info.kind
@@ -516,11 +508,7 @@ class ApiServerFrontend:
                 try:
                     replay = self.server.events_since(api_version, kind, namespace, rv_param)
                 except ExpiredError as e:
-                    payload = json.dumps(_status_body(e), separators=(",", ":")).encode()
-                    writer.write(
-                        (f"HTTP/1.1 410 Gone\r\nContent-Type: application/json\r\n"
-                         f"Content-Length: {len(payload)}\r\n\r\n").encode() + payload
-                    )
+                    writer.write(wirecodec.frame(_json_prefix(410), _status_body(e)))
                     await writer.drain()
                     return
                 try:
@@ -551,7 +539,7 @@ class ApiServerFrontend:
                 last_rv = max(last_rv, self._ev_rv(ev))
                 if not _matches(ev.get("object") or {}):
                     continue
-                writer.write((json.dumps(ev, separators=(",", ":")) + "\n").encode())
+                writer.write(wirecodec.dumpb(ev) + b"\n")
             await writer.drain()
             # watch budget: like a real apiserver, an expiring watch ends
             # with a clean stream close and the client resumes from its rv
@@ -572,7 +560,7 @@ class ApiServerFrontend:
                         continue  # already covered by the replay snapshot
                     if not _matches(ev.get("object") or {}):
                         continue
-                    writer.write((json.dumps(ev, separators=(",", ":")) + "\n").encode())
+                    writer.write(wirecodec.dumpb(ev) + b"\n")
                     await writer.drain()
             finally:
                 if budget_handle is not None:

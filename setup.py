@@ -1,6 +1,6 @@
 """Build script: package + the optional native hot-path extension.
 
-`python setup.py build_ext --inplace` compiles native/_amcore.c into
+`python setup.py build_ext --inplace` compiles native/*.c into
 active_monitor_amd/ so the in-tree .so ships with source checkouts. The
 package works without it (pure-Python fallback in utils/fastcopy.py)."""
 import os
@@ -29,7 +29,10 @@ setup(
     ext_modules=[
         Extension(
             "active_monitor_amd._amcore",
-            sources=[os.path.join("native", "_amcore.c")],
+            sources=[os.path.join("native", name) for name in
+                     ("_amcore.c", "wirejson.c", "wirehead.c")],
+            depends=[os.path.join("native", name) for name in
+                     ("wirejson.h", "wirehead.h")],
             extra_compile_args=["-O2"],
         )
     ],
