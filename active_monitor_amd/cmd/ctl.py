@@ -23,7 +23,13 @@ import yaml
 from .. import API_VERSION
 from ..api.types import parse_k8s_time
 from ..kube.config import get_config
-from ..kube.errors import AlreadyExistsError, ConflictError, NotFoundError
+from ..kube.errors import (
+    AlreadyExistsError,
+    BadRequestError,
+    ConflictError,
+    InvalidError,
+    NotFoundError,
+)
 from ..kube.http import HttpClient
 from ..kube.registry import WF_API_VERSION
 
@@ -116,27 +122,41 @@ async def cmd_describe(client: HttpClient, args) -> int:
     return 0
 
 
+async def _apply_one(client: HttpClient, doc: Dict[str, Any], mode: str) -> None:
+    meta = doc.get("metadata") or {}
+    name = meta.get("name", "")
+    try:
+        await client.create(doc, field_validation=mode)
+        print(f'{doc.get("kind", "object").lower()}/{name} created')
+    except (AlreadyExistsError, ConflictError):
+        # exists: update with a fresh resourceVersion
+        current = await client.get(
+            doc.get("apiVersion", ""), doc.get("kind", ""),
+            meta.get("namespace", ""), name,
+        )
+        doc.setdefault("metadata", {})["resourceVersion"] = (
+            current["metadata"]["resourceVersion"]
+        )
+        await client.update(doc, field_validation=mode)
+        print(f'{doc.get("kind", "object").lower()}/{name} configured')
+
+
 async def cmd_apply(client: HttpClient, args) -> int:
     with open(args.filename) as f:
         docs = [d for d in yaml.safe_load_all(f) if d]
+    # kubectl's --validate values, as the fieldValidation the server reads
+    mode = args.validate.capitalize()
+    rc = 0
     for doc in docs:
-        meta = doc.get("metadata") or {}
-        name = meta.get("name", "")
         try:
-            await client.create(doc)
-            print(f'{doc.get("kind", "object").lower()}/{name} created')
-        except (AlreadyExistsError, ConflictError):
-            # exists: update with a fresh resourceVersion
-            current = await client.get(
-                doc.get("apiVersion", ""), doc.get("kind", ""),
-                meta.get("namespace", ""), name,
-            )
-            doc.setdefault("metadata", {})["resourceVersion"] = (
-                current["metadata"]["resourceVersion"]
-            )
-            await client.update(doc)
-            print(f'{doc.get("kind", "object").lower()}/{name} configured')
-    return 0
+            await _apply_one(client, doc, mode)
+        except (InvalidError, BadRequestError) as e:
+            # a refused document does not stop the ones after it
+            print(f"error: {e.message}", file=sys.stderr)
+            rc = 1
+        while client.warnings:
+            print(f"Warning: {client.warnings.popleft()}", file=sys.stderr)
+    return rc
 
 
 async def cmd_delete(client: HttpClient, args) -> int:
@@ -168,6 +188,12 @@ def build_parser() -> argparse.ArgumentParser:
 
     a = sub.add_parser("apply")
     a.add_argument("-f", "--filename", required=True)
+    a.add_argument("--validate", choices=["strict", "warn", "ignore"],
+                   default="strict",
+                   help="what the server does with fields its schema does "
+                        "not know: strict refuses the document, warn stores "
+                        "it without them and says so, ignore stores it "
+                        "without them silently (default: strict, as kubectl)")
 
     rm = sub.add_parser("delete")
     rm.add_argument("resource", choices=sorted(ALIASES))

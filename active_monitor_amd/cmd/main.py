@@ -82,6 +82,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="memory backend: keep the store in DIR (snapshot + "
                         "journal) so HealthChecks, counters and workflows "
                         "survive a restart; one process per directory")
+    p.add_argument("--no-schema-validation", dest="schema_validation",
+                   action="store_false",
+                   help="memory backend: store HealthChecks as given instead "
+                        "of validating and pruning them by the CRD schema "
+                        "(also: AM_SCHEMA_VALIDATION=0 in the environment)")
     p.add_argument("--shard-index", type=int, default=0,
                    help="this controller's shard (keyspace split by CR-name hash)")
     p.add_argument("--shard-count", type=int, default=1,
@@ -155,19 +160,24 @@ async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
             await client.close()
             return 1
     else:
+        from ..kube.standalone import standalone_schemas
+
+        schemas, schema_line = standalone_schemas(
+            getattr(args, "schema_validation", True))
+        log.info(schema_line)
         data_dir = getattr(args, "data_dir", None)
         if data_dir:
             from ..kube.persist import StoreError
 
             try:
-                store = MemoryApiServer.open(data_dir)
+                store = MemoryApiServer.open(data_dir, schemas=schemas)
             except (StoreError, OSError) as e:
                 log.error("cannot open data directory: %s", e)
                 return 1
             log.info("data directory %s: loaded %d objects, resourceVersion %s",
                      store.data_dir, len(store), store.resource_version())
         else:
-            store = MemoryApiServer()
+            store = MemoryApiServer(schemas=schemas)
         client = MemoryClient(store)
         if args.workflow_engine == "local":
             from ..workflow import LocalWorkflowEngine
@@ -254,6 +264,8 @@ def main(argv=None) -> int:
     args = parser.parse_args(argv)
     if args.data_dir and args.backend != "memory":
         parser.error("--data-dir applies to --backend memory only")
+    if not args.schema_validation and args.backend != "memory":
+        parser.error("--no-schema-validation applies to --backend memory only")
     try:
         return asyncio.run(run(args))
     except KeyboardInterrupt:

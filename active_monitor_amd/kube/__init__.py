@@ -3,6 +3,7 @@ from .client import EventRecorder, FakeRecorder, KubeClient, MemoryClient
 from .errors import (
     AlreadyExistsError,
     ApiError,
+    BadRequestError,
     ConflictError,
     InvalidError,
     NotFoundError,
@@ -13,12 +14,13 @@ from .errors import (
     is_not_found,
     is_storage_error,
 )
-from .memory import MemoryApiServer, Subscription
+from .memory import MemoryApiServer, Subscription, healthcheck_schemas
 from .registry import DEFAULT_REGISTRY, WF_API_VERSION, WF_KIND, WF_PLURAL, Registry, ResourceInfo
 
 __all__ = [
     "AlreadyExistsError",
     "ApiError",
+    "BadRequestError",
     "ConflictError",
     "DEFAULT_REGISTRY",
     "EventRecorder",
@@ -36,6 +38,7 @@ __all__ = [
     "WF_KIND",
     "WF_PLURAL",
     "contains_equal_fold_substring",
+    "healthcheck_schemas",
     "ignore_not_found",
     "is_conflict",
     "is_not_found",

@@ -80,17 +80,33 @@ class MemoryClient:
         return self.server.list(api_version, kind, namespace, label_selector,
                                 snapshot_read, field_selector)
 
-    async def create(self, obj: Obj, transfer: bool = False) -> Obj:
-        await self._lat()
-        return self.server.create(obj, transfer)
+    # field_validation / warnings: see MemoryApiServer.create
 
-    async def update(self, obj: Obj) -> Obj:
+    async def create(self, obj: Obj, transfer: bool = False,
+                     field_validation: str = "Warn",
+                     warnings: Optional[List[str]] = None) -> Obj:
         await self._lat()
-        return self.server.update(obj)
+        return self.server.create(obj, transfer, field_validation, warnings)
 
-    async def update_status(self, obj: Obj) -> Obj:
+    async def update(self, obj: Obj, field_validation: str = "Warn",
+                     warnings: Optional[List[str]] = None) -> Obj:
         await self._lat()
-        return self.server.update_status(obj)
+        return self.server.update(obj, field_validation, warnings)
+
+    async def update_status(self, obj: Obj, field_validation: str = "Warn",
+                            warnings: Optional[List[str]] = None) -> Obj:
+        await self._lat()
+        return self.server.update_status(obj, field_validation, warnings)
+
+    async def patch(self, api_version: str, kind: str, namespace: str, name: str,
+                    patch: Obj, subresource: str = "",
+                    field_validation: str = "Warn",
+                    warnings: Optional[List[str]] = None) -> Obj:
+        await self._lat()
+        return self.server.patch(api_version, kind, namespace, name, patch,
+                                 subresource=subresource,
+                                 field_validation=field_validation,
+                                 warnings=warnings)
 
     async def delete(self, api_version: str, kind: str, namespace: str, name: str) -> None:
         await self._lat()

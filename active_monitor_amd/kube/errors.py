@@ -39,8 +39,26 @@ class ConflictError(ApiError):
 
 
 class InvalidError(ApiError):
+    """422. ``causes`` lists the single field errors of a schema rejection
+    as ``{"reason", "message", "field"}`` dicts (``details.causes`` of the
+    Status body); ``details`` is that Status body's whole ``details``."""
+
     code = 422
     reason = "Invalid"
+
+    def __init__(self, message: str = "", causes: Optional[list] = None,
+                 details: Optional[dict] = None):
+        super().__init__(message)
+        self.causes = list(causes) if causes else []
+        self.details = details
+
+
+class BadRequestError(ApiError):
+    """400: the request could not be decoded — under strict field validation,
+    an object that names fields the schema does not know."""
+
+    code = 400
+    reason = "BadRequest"
 
 
 class ExpiredError(ApiError):

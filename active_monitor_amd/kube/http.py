@@ -11,6 +11,7 @@ from __future__ import annotations
 import asyncio
 import json
 import logging
+import re
 import ssl
 import time
 from collections import deque
@@ -24,6 +25,7 @@ from .auth import Credential, CredentialSource
 from .errors import (
     AlreadyExistsError,
     ApiError,
+    BadRequestError,
     ConflictError,
     InvalidError,
     NotFoundError,
@@ -39,11 +41,13 @@ Obj = Dict[str, Any]
 def _error_for(status: int, body: str) -> ApiError:
     reason = ""
     message = body
+    details = None
     try:
         parsed = json.loads(body)
         reason = parsed.get("reason", "")
         message = parsed.get("message", body)
-    except (ValueError, TypeError):
+        details = parsed.get("details")
+    except (ValueError, TypeError, AttributeError):
         pass
     if status == 404:
         return NotFoundError(message)
@@ -54,10 +58,27 @@ def _error_for(status: int, body: str) -> ApiError:
             return AlreadyExistsError(message)
         return ConflictError(message)
     if status == 422:
+        if isinstance(details, dict):
+            return InvalidError(message, causes=details.get("causes"),
+                                details=details)
         return InvalidError(message)
+    if status == 400 and reason == "BadRequest":
+        return BadRequestError(message)
     err = ApiError(message)
     err.code = status
     return err
+
+
+_WARNING_HEADER = re.compile(r'^\s*\d{3}\s+\S+\s+"((?:[^"\\]|\\.)*)"')
+
+
+def _warning_text(header: str) -> str:
+    """The warn-text of an RFC 7234 ``Warning`` header value
+    (``299 - "text"``), unquoted; the raw value when it is not one."""
+    m = _WARNING_HEADER.match(header)
+    if m is None:
+        return header.strip()
+    return re.sub(r"\\(.)", r"\1", m.group(1))
 
 
 def _as_text(raw: Union[bytes, str]) -> str:
@@ -434,6 +455,10 @@ class HttpClient:
         self._limiter = _TokenBucket(qps, burst)
         #: unary requests issued (observability/bench; watch streams excluded)
         self.request_count = 0
+        #: the latest apiserver warnings (``Warning`` response headers, e.g.
+        #: ``unknown field "spec.x"``). Only requests sent with
+        #: ``field_validation`` set see response headers and add here.
+        self.warnings: "deque[str]" = deque(maxlen=256)
 
     async def start(self) -> None:
         headers = {"Content-Type": "application/json"}
@@ -568,15 +593,43 @@ class HttpClient:
         ) as resp:
             return resp.status, await resp.text()
 
-    async def _send_patch(self, path: str, patch: Obj,
-                          cred: Optional[Credential]) -> Tuple[int, str]:
-        headers = {"Content-Type": "application/merge-patch+json"}
+    async def _send_session(self, method: str, path: str, body: Obj,
+                            content_type: str,
+                            params: Optional[Dict[str, str]],
+                            cred: Optional[Credential]) -> Tuple[int, str]:
+        """One request through the aiohttp session: the path with control
+        over request headers and sight of response headers."""
+        headers = {"Content-Type": content_type}
         if cred is not None:
             headers["Authorization"] = f"Bearer {cred.token}"
-        async with self._session.patch(
-            self.base_url + path, data=wirecodec.dumpb(patch), headers=headers,
+        async with self._session.request(
+            method, self.base_url + path, data=wirecodec.dumpb(body),
+            headers=headers, params=params,
         ) as resp:
+            for value in resp.headers.getall("Warning", ()):
+                text = _warning_text(value)
+                log.warning("apiserver warning: %s", text)
+                self.warnings.append(text)
             return resp.status, await resp.text()
+
+    async def _request_validated(self, method: str, path: str, body: Obj,
+                                 field_validation: Optional[str],
+                                 content_type: str = "application/json") -> Obj:
+        """A write that names its ``fieldValidation`` (or a patch): off the
+        pooled fast path, through the session."""
+        params = {"fieldValidation": field_validation} if field_validation else None
+        await self._limiter.acquire()
+        self.request_count += 1
+        if self._credentials is not None:
+            return await self._with_credentials(
+                lambda cred: self._send_session(
+                    method, path, body, content_type, params, cred)
+            )
+        status, text = await self._send_session(
+            method, path, body, content_type, params, None)
+        if status >= 400:
+            raise _error_for(status, text)
+        return json.loads(text) if text else {}
 
     async def get(self, api_version: str, kind: str, namespace: str, name: str,
                   snapshot_read: bool = False) -> Obj:
@@ -599,47 +652,54 @@ class HttpClient:
         )
         return out.get("items", [])
 
-    async def create(self, obj: Obj, transfer: bool = False) -> Obj:
+    # ``field_validation`` ("Strict", "Warn" or "Ignore") is sent as the
+    # ``fieldValidation`` query parameter. None — what the controller sends —
+    # leaves it out (the apiserver then warns) and stays on the pooled path,
+    # which does not look at response headers.
+
+    async def create(self, obj: Obj, transfer: bool = False,
+                     field_validation: Optional[str] = None) -> Obj:
         # transfer is a memory-backend optimization; ignored on the wire
         meta = obj.get("metadata") or {}
         path = self._collection_path(
             obj.get("apiVersion", ""), obj.get("kind", ""), meta.get("namespace")
         )
+        if field_validation is not None:
+            return await self._request_validated("POST", path, obj, field_validation)
         return await self._request("POST", path, obj)
 
-    async def update(self, obj: Obj) -> Obj:
+    async def update(self, obj: Obj, field_validation: Optional[str] = None) -> Obj:
         meta = obj.get("metadata") or {}
         path = self._object_path(
             obj.get("apiVersion", ""), obj.get("kind", ""),
             meta.get("namespace", ""), meta.get("name", ""),
         )
+        if field_validation is not None:
+            return await self._request_validated("PUT", path, obj, field_validation)
         return await self._request("PUT", path, obj)
 
-    async def update_status(self, obj: Obj) -> Obj:
+    async def update_status(self, obj: Obj,
+                            field_validation: Optional[str] = None) -> Obj:
         meta = obj.get("metadata") or {}
         path = self._object_path(
             obj.get("apiVersion", ""), obj.get("kind", ""),
             meta.get("namespace", ""), meta.get("name", ""),
         ) + "/status"
+        if field_validation is not None:
+            return await self._request_validated("PUT", path, obj, field_validation)
         return await self._request("PUT", path, obj)
 
     async def patch(self, api_version: str, kind: str, namespace: str, name: str,
-                    patch: Obj, subresource: str = "") -> Obj:
+                    patch: Obj, subresource: str = "",
+                    field_validation: Optional[str] = None) -> Obj:
         """JSON merge-patch (kubectl patch semantics). Not on the reconcile
         hot path — goes through the full aiohttp session for header control."""
         path = self._object_path(api_version, kind, namespace, name)
         if subresource:
             path += f"/{subresource}"
-        await self._limiter.acquire()
-        self.request_count += 1
-        if self._credentials is not None:
-            return await self._with_credentials(
-                lambda cred: self._send_patch(path, patch, cred)
-            )
-        status, text = await self._send_patch(path, patch, None)
-        if status >= 400:
-            raise _error_for(status, text)
-        return json.loads(text) if text else {}
+        return await self._request_validated(
+            "PATCH", path, patch, field_validation,
+            content_type="application/merge-patch+json")
 
     async def delete(self, api_version: str, kind: str, namespace: str, name: str) -> None:
         await self._request("DELETE", self._object_path(api_version, kind, namespace, name))

@@ -18,6 +18,11 @@ exercises:
 The core is synchronous and thread-safe; watches are asyncio queues fed via
 ``call_soon_threadsafe`` so any thread may mutate the store.
 
+With a schema installed for a kind (``schemas=`` / :meth:`install_schema`,
+see :mod:`.schema`) every write of that kind is validated and pruned like a
+real apiserver validates a custom resource against its CRD; with none — the
+default — writes are stored as given.
+
 ``MemoryApiServer()`` lives and dies with the process.
 ``MemoryApiServer.open(data_dir)`` is the same store journaled to a directory
 (:mod:`.persist`), for standalone deployments that must survive a restart.
@@ -34,6 +39,7 @@ from ..api.types import k8s_now
 from ..utils.fastcopy import deep_copy, snapshot
 from .errors import (
     AlreadyExistsError,
+    BadRequestError,
     ConflictError,
     ExpiredError,
     InvalidError,
@@ -43,6 +49,25 @@ from .registry import DEFAULT_REGISTRY, STATUS_SUBRESOURCE_KINDS, Registry
 
 Obj = Dict[str, Any]
 Key = Tuple[str, str, str, str]  # (apiVersion, kind, namespace, name)
+
+FIELD_VALIDATION_MODES = ("Warn", "Strict", "Ignore")
+_HC_SCHEMAS: Dict[Tuple[str, str], Any] = {}
+
+
+def healthcheck_schemas() -> Dict[Tuple[str, str], Any]:
+    """``{(apiVersion, kind): Validator}`` for the HealthCheck CRD as
+    ``api.crd.healthcheck_crd()`` generates it — the ``schemas=`` argument
+    of a store that validates HealthChecks. Compiled once per process."""
+    if not _HC_SCHEMAS:
+        from ..api.crd import healthcheck_crd
+        from .schema import compile_schema
+
+        spec = healthcheck_crd()["spec"]
+        for version in spec["versions"]:
+            _HC_SCHEMAS[(f'{spec["group"]}/{version["name"]}',
+                         spec["names"]["kind"])] = compile_schema(
+                version["schema"]["openAPIV3Schema"])
+    return dict(_HC_SCHEMAS)
 
 _SUFFIX_ALPHABET = "bcdfghjklmnpqrstvwxz2456789"  # k8s-style name suffix chars
 _suffix_counter = [random.randrange(27 ** 4)]
@@ -167,11 +192,19 @@ class Subscription:
 
 
 class MemoryApiServer:
-    def __init__(self, registry: Registry = DEFAULT_REGISTRY):
+    def __init__(self, registry: Registry = DEFAULT_REGISTRY,
+                 schemas: Optional[Dict[Tuple[str, str], Any]] = None):
         self.registry = registry
+        # (apiVersion, kind) → compiled Validator; a kind without an entry is
+        # stored unvalidated. Empty (the default) costs writes one falsy test.
+        self._schemas: Dict[Tuple[str, str], Any] = {}
+        #: writes refused by admission (422 Invalid, or 400 under Strict)
+        self.rejected_writes = 0
         self._objects: Dict[Key, Obj] = {}
         self._rv = 0
         self._lock = threading.RLock()
+        for (av, kind), schema in (schemas or {}).items():
+            self.install_schema(av, kind, schema)
         self._subs: List[Subscription] = []
         # ownerReference uid → dependent keys (O(1) cascade GC)
         self._by_owner: Dict[str, set] = {}
@@ -198,7 +231,9 @@ class MemoryApiServer:
     @classmethod
     def open(cls, data_dir: str, registry: Registry = DEFAULT_REGISTRY,
              sync_interval: float = 1.0,
-             compact_threshold: int = 4096) -> "MemoryApiServer":
+             compact_threshold: int = 4096,
+             schemas: Optional[Dict[Tuple[str, str], Any]] = None,
+             ) -> "MemoryApiServer":
         """A store that survives the process: state is loaded from
         ``data_dir`` (created if missing) and every mutation is journaled
         there before it becomes visible. A kill of the process loses nothing
@@ -223,10 +258,15 @@ class MemoryApiServer:
 
         The watch history restarts empty with the compaction horizon at the
         restored resourceVersion: a watch resuming from before the restart
-        gets 410 Gone and re-lists, one resuming exactly there is valid."""
+        gets 410 Gone and re-lists, one resuming exactly there is valid.
+
+        ``schemas`` applies to writes from now on: objects already in the
+        directory are loaded as they are, not re-validated (a real apiserver
+        does not re-validate what etcd holds either). Such an object is
+        refused the next time someone writes it back unchanged."""
         from .persist import Journal
 
-        self = cls(registry)
+        self = cls(registry, schemas)
         journal = Journal(data_dir, sync_interval, compact_threshold)
         try:
             rv, objects = journal.load(self._key)
@@ -253,6 +293,61 @@ class MemoryApiServer:
         with self._lock:
             if self._journal is not None and not self._journal.closed:
                 self._journal.close()
+
+    # -- admission -----------------------------------------------------------
+
+    @staticmethod
+    def _check_mode(field_validation: str) -> None:
+        """Every write checks its mode on entry: a wrong one is refused
+        whether or not a schema is installed or anything would be pruned."""
+        if field_validation not in FIELD_VALIDATION_MODES:
+            raise BadRequestError(
+                f'invalid fieldValidation "{field_validation}": supported '
+                'values: ' + ", ".join(f'"{m}"' for m in FIELD_VALIDATION_MODES))
+
+    def install_schema(self, api_version: str, kind: str,
+                       openapi_schema: Any) -> None:
+        """Validate and prune every later write of ``kind`` by this
+        ``openAPIV3Schema`` (a dict, or one already compiled by
+        :func:`.schema.compile_schema`)."""
+        if isinstance(openapi_schema, dict):
+            from .schema import compile_schema
+
+            openapi_schema = compile_schema(openapi_schema)
+        with self._lock:
+            self._schemas[(api_version, kind)] = openapi_schema
+
+    def _admit(self, validator: Any, obj: Obj, field_validation: str,
+               warnings: Optional[List[str]], subtree: Optional[str] = None) -> None:
+        """Run under the lock, before anything of the write is visible: on a
+        refusal the store, the rv counter, the history and the journal are
+        as they were."""
+        pruned, errs = validator.admit(obj, subtree=subtree)
+        if not errs and not pruned:
+            return
+        api_version, kind = obj.get("apiVersion", ""), obj.get("kind", "")
+        group, _, version = api_version.rpartition("/")
+        if errs:
+            self.rejected_writes += 1
+            name = (obj.get("metadata") or {}).get("name", "") or ""
+            listed = errs[0] if len(errs) == 1 else "[" + ", ".join(errs) + "]"
+            qualified = f"{kind}.{group}" if group else kind
+            causes = [{"reason": e.reason, "message": e.detail, "field": e.field}
+                      for e in errs]
+            raise InvalidError(
+                f'{qualified} "{name}" is invalid: {listed}', causes=causes,
+                details={"name": name, "group": group, "kind": kind,
+                         "causes": causes},
+            )
+        if field_validation == "Strict":
+            self.rejected_writes += 1
+            unknown = ", ".join(f'unknown field "{p}"' for p in pruned)
+            raise BadRequestError(
+                f'{kind} in version "{version}" cannot be handled as a {kind}: '
+                f"strict decoding error: {unknown}"
+            )
+        if field_validation == "Warn" and warnings is not None:
+            warnings.extend(pruned)
 
     # -- internals ---------------------------------------------------------
 
@@ -352,11 +447,23 @@ class MemoryApiServer:
 
     # -- public API --------------------------------------------------------
 
-    def create(self, obj: Obj, transfer: bool = False) -> Obj:
+    def create(self, obj: Obj, transfer: bool = False,
+               field_validation: str = "Warn",
+               warnings: Optional[List[str]] = None) -> Obj:
         """``transfer=True`` lets the store take ownership of ``obj`` (no
         copy-in) and return a read-optimized snapshot (no copy-out). Only for
         callers that built the dict themselves and never touch it again —
-        the controller's submit/event/RBAC paths."""
+        the controller's submit/event/RBAC paths.
+
+        For a kind with a schema installed, here and in :meth:`update`,
+        :meth:`update_status` and :meth:`patch`: an object that violates it
+        raises :class:`InvalidError`; fields it does not know are pruned, and
+        ``field_validation`` decides what else happens to them — ``"Strict"``
+        raises :class:`BadRequestError`, ``"Warn"`` appends their paths to
+        the ``warnings`` list when one is given, ``"Ignore"`` says nothing.
+        Any other mode raises :class:`BadRequestError`, always."""
+        if field_validation != "Warn":
+            self._check_mode(field_validation)
         if not transfer:
             obj = deep_copy(obj)
         meta = obj.setdefault("metadata", {})
@@ -374,6 +481,13 @@ class MemoryApiServer:
                         break
                 else:
                     raise AlreadyExistsError(f"could not generate unique name for {gen}")
+            # named first, as the apiserver does, so that a refusal can say
+            # which object; nothing of the write is visible yet
+            if self._schemas:
+                validator = self._schemas.get(
+                    (obj.get("apiVersion", ""), obj.get("kind", "")))
+                if validator is not None:
+                    self._admit(validator, obj, field_validation, warnings)
             key = self._key(obj)
             if key in self._objects:
                 raise AlreadyExistsError(
@@ -444,7 +558,10 @@ class MemoryApiServer:
                 out.append(copier(obj))
             return out
 
-    def update(self, obj: Obj) -> Obj:
+    def update(self, obj: Obj, field_validation: str = "Warn",
+               warnings: Optional[List[str]] = None) -> Obj:
+        if field_validation != "Warn":
+            self._check_mode(field_validation)
         obj = deep_copy(obj)
         key = self._key(obj)
         meta = obj.setdefault("metadata", {})
@@ -472,6 +589,10 @@ class MemoryApiServer:
                     obj["status"] = deep_copy(existing["status"])
                 else:
                     obj.pop("status", None)
+            if self._schemas:
+                validator = self._schemas.get((key[0], key[1]))
+                if validator is not None:
+                    self._admit(validator, obj, field_validation, warnings)
             # no-op updates don't bump the resourceVersion or emit watch
             # events (apiserver semantics — prevents self-triggering loops)
             meta["resourceVersion"] = ex_meta.get("resourceVersion")
@@ -497,7 +618,10 @@ class MemoryApiServer:
             out = deep_copy(obj)
         return out
 
-    def update_status(self, obj: Obj) -> Obj:
+    def update_status(self, obj: Obj, field_validation: str = "Warn",
+                      warnings: Optional[List[str]] = None) -> Obj:
+        if field_validation != "Warn":
+            self._check_mode(field_validation)
         obj = deep_copy(obj)
         key = self._key(obj)
         meta = obj.get("metadata") or {}
@@ -514,6 +638,11 @@ class MemoryApiServer:
                     f'"{meta.get("name")}": the object has been modified; please apply '
                     f"your changes to the latest version and try again"
                 )
+            if self._schemas:
+                validator = self._schemas.get((key[0], key[1]))
+                if validator is not None:
+                    self._admit(validator, obj, field_validation, warnings,
+                                subtree="status")
             updated = snapshot(existing)
             if "status" in obj:
                 updated["status"] = deep_copy(obj["status"])
@@ -542,12 +671,17 @@ class MemoryApiServer:
                 base[k] = deep_copy(v) if isinstance(v, (dict, list)) else v
 
     def patch(self, api_version: str, kind: str, namespace: str, name: str,
-              patch_obj: Obj, subresource: str = "", upsert: bool = False) -> Obj:
+              patch_obj: Obj, subresource: str = "", upsert: bool = False,
+              field_validation: str = "Warn",
+              warnings: Optional[List[str]] = None) -> Obj:
         """Merge-patch an object (kubectl patch / the merge half of kubectl
         apply). ``subresource='status'`` touches only status; a plain patch
         cannot touch status for kinds with the subresource (enforced by the
         update path it reuses). ``upsert=True`` creates the object when
-        absent (server-side-apply shape)."""
+        absent (server-side-apply shape). With a schema installed it is the
+        merged result that is validated, not the patch."""
+        if field_validation != "Warn":
+            self._check_mode(field_validation)
         info = self.registry.by_kind(api_version, kind)
         ns = namespace if info.namespaced else ""
         with self._lock:
@@ -562,14 +696,16 @@ class MemoryApiServer:
                 meta.setdefault("name", name)
                 if info.namespaced:
                     meta.setdefault("namespace", namespace)
-                return self.create(obj, transfer=True)
+                return self.create(obj, transfer=True,
+                                   field_validation=field_validation,
+                                   warnings=warnings)
             merged = deep_copy(existing)
             if subresource == "status":
                 status = merged.setdefault("status", {})
                 patch_status = patch_obj.get("status")
                 if isinstance(patch_status, dict):
                     self._merge(status, patch_status)
-                return self.update_status(merged)
+                return self.update_status(merged, field_validation, warnings)
             self._merge(merged, deep_copy(patch_obj))
             # identity is immutable under patch
             merged["apiVersion"], merged["kind"] = api_version, kind
@@ -581,7 +717,7 @@ class MemoryApiServer:
             # otherwise patch applies to the current version
             if "resourceVersion" not in (patch_obj.get("metadata") or {}):
                 m["resourceVersion"] = existing["metadata"].get("resourceVersion")
-            return self.update(merged)
+            return self.update(merged, field_validation, warnings)
 
     def delete(self, api_version: str, kind: str, namespace: str, name: str) -> None:
         info = self.registry.by_kind(api_version, kind)

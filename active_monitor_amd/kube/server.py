@@ -60,7 +60,7 @@ def _json_prefix(status: int) -> bytes:
 
 
 def _status_body(err: ApiError) -> dict:
-    return {
+    body = {
         "kind": "Status",
         "apiVersion": "v1",
         "status": "Failure",
@@ -68,6 +68,46 @@ def _status_body(err: ApiError) -> dict:
         "reason": err.reason,
         "code": err.code,
     }
+    details = getattr(err, "details", None)
+    if details:  # a schema rejection: name, group, kind and the causes
+        body["details"] = details
+    return body
+
+
+class _Warned:
+    """A response object that goes out with ``Warning`` headers: what a write
+    returns when fields were pruned under ``fieldValidation=Warn``. Every
+    other JSON response is a plain dict, and the writer tells the two apart
+    by the one type test it made before there were warnings."""
+
+    __slots__ = ("obj", "paths")
+
+    def __init__(self, obj: dict, paths: list):
+        self.obj = obj
+        self.paths = paths
+
+    @staticmethod
+    def _header_text(path: str) -> str:
+        """``path`` as it may stand in a quoted header value. Its keys are
+        the client's own JSON keys, so anything but printable ASCII — CR and
+        LF above all — goes out percent-encoded (as does ``%`` itself), and
+        backslash and double quote are backslash-escaped."""
+        out = []
+        for byte in path.encode("utf-8", "surrogatepass"):
+            if byte in (0x22, 0x5C):
+                out.append("\\" + chr(byte))
+            elif 0x20 <= byte <= 0x7E and byte != 0x25:
+                out.append(chr(byte))
+            else:
+                out.append(f"%{byte:02X}")
+        return "".join(out)
+
+    def prefix(self, status: int) -> bytes:
+        lines = "".join(
+            f'Warning: 299 - "unknown field \\"{self._header_text(p)}\\""\r\n'
+            for p in self.paths
+        )
+        return _json_prefix(status) + lines.encode("ascii")
 
 
 #: served without credentials, as on a real apiserver
@@ -173,7 +213,11 @@ class ApiServerFrontend:
                 if (flags & WANT_TABLE and method == "GET" and status == 200
                         and isinstance(obj, dict)):
                     obj = self._to_table(obj)
-                if isinstance(obj, str):  # health probes are plain text
+                if type(obj) is dict:
+                    writer.write(wirecodec.frame(_json_prefix(status), obj))
+                elif isinstance(obj, _Warned):
+                    writer.write(wirecodec.frame(obj.prefix(status), obj.obj))
+                elif isinstance(obj, str):  # health probes are plain text
                     payload = obj.encode()
                     writer.write(
                         (
@@ -315,12 +359,12 @@ class ApiServerFrontend:
                 meta = obj.setdefault("metadata", {})
                 if namespace and not meta.get("namespace"):
                     meta["namespace"] = namespace
-                return 201, self.server.create(obj)
+                return self._write(201, query, self.server.create, obj)
             if method == "PUT":
                 obj = self._parse_body(body)
                 if subresource == "status":
-                    return 200, self.server.update_status(obj)
-                return 200, self.server.update(obj)
+                    return self._write(200, query, self.server.update_status, obj)
+                return self._write(200, query, self.server.update, obj)
             if method == "DELETE" and not name:
                 # deletecollection (kubectl delete --all / -l selector)
                 victims = self.server.list(
@@ -359,7 +403,8 @@ class ApiServerFrontend:
                 else:  # merge-patch / strategic-merge-patch
                     patch_obj = self._parse_body(body)
                     upsert = False
-                return 200, self.server.patch(
+                return self._write(
+                    200, query, self.server.patch,
                     api_version, kind, namespace, name, patch_obj,
                     subresource=subresource, upsert=upsert,
                 )
@@ -369,6 +414,21 @@ class ApiServerFrontend:
         except ApiError as e:
             return e.code, _status_body(e)
         return 405, _status_body(ApiError(f"unsupported method {method}"))
+
+    @staticmethod
+    def _write(status: int, query: dict, write, *args, **kwargs):
+        """Run one store write under the request's ``fieldValidation`` (absent
+        means Warn, as in Kubernetes 1.27 and later). Pruned paths come back
+        in ``warnings`` only under Warn, with a schema installed for the
+        kind; the usual answer is the plain object."""
+        mode = query.get("fieldValidation")
+        if mode is None:
+            mode = "Warn"  # any other value is checked by the store
+        warnings: list = []
+        out = write(*args, field_validation=mode, warnings=warnings, **kwargs)
+        if warnings:
+            return status, _Warned(out, warnings)
+        return status, out
 
     @staticmethod
     def _parse_body(body: bytes) -> dict:

@@ -22,10 +22,11 @@ from __future__ import annotations
 import argparse
 import asyncio
 import json
+import os
 import signal
 import sys
 
-from .memory import MemoryApiServer
+from .memory import MemoryApiServer, healthcheck_schemas
 from .server import ApiServerFrontend
 
 
@@ -74,7 +75,22 @@ def parse_args(argv=None):
                    help="keep the store in DIR (snapshot + journal) so a "
                         "restart finds every object again; one process per "
                         "directory (default: memory only)")
+    p.add_argument("--no-schema-validation", dest="schema_validation",
+                   action="store_false",
+                   help="store HealthChecks as given instead of validating "
+                        "and pruning them by the CRD schema (also: "
+                        "AM_SCHEMA_VALIDATION=0 in the environment)")
     return p.parse_args(argv)
+
+
+def standalone_schemas(enabled: bool = True):
+    """``(schemas, log line)`` for a standalone store: the HealthCheck CRD
+    schema, unless ``enabled`` is false or AM_SCHEMA_VALIDATION=0 is set."""
+    if not enabled or os.environ.get("AM_SCHEMA_VALIDATION") == "0":
+        return None, "schema validation: off"
+    schemas = healthcheck_schemas()
+    kinds = ", ".join(f"{kind} ({av})" for av, kind in schemas)
+    return schemas, f"schema validation: {kinds}"
 
 
 def read_accepted_tokens(path: str) -> set:
@@ -85,14 +101,14 @@ def read_accepted_tokens(path: str) -> set:
     return tokens
 
 
-def open_durable_store(data_dir: str):
+def open_durable_store(data_dir: str, schemas=None):
     """Open the store kept in ``data_dir`` and say what was found; on a
     locked or unreadable directory print the reason and return None — the
     caller exits 1 and never starts an empty store over it."""
     from .persist import StoreError
 
     try:
-        server = MemoryApiServer.open(data_dir)
+        server = MemoryApiServer.open(data_dir, schemas=schemas)
     except (StoreError, OSError) as e:
         print(f"cannot open data directory: {e}", file=sys.stderr, flush=True)
         return None
@@ -105,13 +121,16 @@ def open_durable_store(data_dir: str):
 async def amain(args) -> int:
     from .client import MemoryClient
 
+    schemas, schema_line = standalone_schemas(
+        getattr(args, "schema_validation", True))
+    print(schema_line, file=sys.stderr, flush=True)
     data_dir = getattr(args, "data_dir", None)
     if data_dir:
-        server = open_durable_store(data_dir)
+        server = open_durable_store(data_dir, schemas)
         if server is None:
             return 1
     else:
-        server = MemoryApiServer()
+        server = MemoryApiServer(schemas=schemas)
     accepted = None
     if getattr(args, "token_file", None):
         accepted = read_accepted_tokens(args.token_file)

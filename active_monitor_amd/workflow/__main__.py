@@ -2,8 +2,11 @@
 
 ``lint FILE...``
     Check Workflow or HealthCheck YAML against the surface the local executor
-    supports. For a HealthCheck the inline check and remedy workflows are
-    linted. Prints one line per problem; exit status 1 when there are any.
+    supports. A HealthCheck is first held against the CRD schema the way a
+    strict ``apply`` would (``invalid HealthCheck: spec.repeatAfterSec: ...``,
+    ``invalid HealthCheck: unknown field "spec.x"``); then its inline check
+    and remedy workflows are linted. Prints one line per problem; exit status
+    1 when there are any.
 
 ``run FILE [-p name=value ...] [--remedy]``
     Execute one workflow with the local executor against a throw-away
@@ -41,6 +44,22 @@ def _inline(wf: Any) -> bool:
     )
 
 
+def _schema_problems(doc: Dict[str, Any]) -> List[str]:
+    """What an apiserver holding the HealthCheck CRD would refuse under
+    strict field validation: schema errors, then unknown fields."""
+    import copy
+
+    from ..kube.memory import healthcheck_schemas
+
+    validator = healthcheck_schemas().get((doc.get("apiVersion"), "HealthCheck"))
+    if validator is None:
+        return []  # another apiVersion: HealthCheck.from_dict has the say
+    pruned, errs = validator.admit(copy.deepcopy(doc))
+    if errs:
+        return [f"invalid HealthCheck: {e}" for e in errs]
+    return [f'invalid HealthCheck: unknown field "{p}"' for p in pruned]
+
+
 def _specs(path: str) -> Iterator[Tuple[str, Optional[Dict[str, Any]], List[str]]]:
     """``(label, spec, problems)`` for every workflow found in ``path``."""
     try:
@@ -56,6 +75,10 @@ def _specs(path: str) -> Iterator[Tuple[str, Optional[Dict[str, Any]], List[str]
             spec = doc.get("spec")
             yield label, spec, [] if isinstance(spec, dict) else ["invalid workflow, missing spec"]
         elif kind == "HealthCheck":
+            problems = _schema_problems(doc)
+            if problems:
+                yield label, None, problems
+                continue
             try:
                 hc = HealthCheck.from_dict(doc)
             except Exception as e:
