@@ -24,18 +24,31 @@ Obj = Dict[str, Any]
 
 
 class KubeClient(Protocol):
-    async def get(self, api_version: str, kind: str, namespace: str, name: str) -> Obj: ...
+    """What both backends implement. ``snapshot_read`` and ``transfer`` let
+    the in-memory backend skip copies (see MemoryApiServer.get and .create)
+    and mean nothing on the wire; ``field_validation`` is "Strict", "Warn" or
+    "Ignore", and each backend's default stands for "not named"."""
+
+    async def get(self, api_version: str, kind: str, namespace: str, name: str,
+                  snapshot_read: bool = False) -> Obj: ...
 
     async def list(
         self, api_version: str, kind: str,
         namespace: Optional[str] = None, label_selector: Optional[str] = None,
+        snapshot_read: bool = False, field_selector: Optional[str] = None,
     ) -> List[Obj]: ...
 
-    async def create(self, obj: Obj) -> Obj: ...
+    async def create(self, obj: Obj, transfer: bool = False,
+                     field_validation: Optional[str] = ...) -> Obj: ...
 
-    async def update(self, obj: Obj) -> Obj: ...
+    async def update(self, obj: Obj, field_validation: Optional[str] = ...) -> Obj: ...
 
-    async def update_status(self, obj: Obj) -> Obj: ...
+    async def update_status(self, obj: Obj,
+                            field_validation: Optional[str] = ...) -> Obj: ...
+
+    async def patch(self, api_version: str, kind: str, namespace: str, name: str,
+                    patch: Obj, subresource: str = "",
+                    field_validation: Optional[str] = ...) -> Obj: ...
 
     async def delete(self, api_version: str, kind: str, namespace: str, name: str) -> None: ...
 
@@ -167,10 +180,7 @@ class EventRecorder:
     async def _write(self, op: str, key: tuple, ev: Obj) -> None:
         if op == "create":
             try:
-                try:
-                    await self.client.create(ev, transfer=True)
-                except TypeError:  # backend without transfer support
-                    await self.client.create(ev)
+                await self.client.create(ev, transfer=True)
             except AlreadyExistsError:
                 # survived a restart (deterministic name): fall through to
                 # an update carrying the new count

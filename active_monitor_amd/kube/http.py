@@ -15,7 +15,7 @@ import re
 import ssl
 import time
 from collections import deque
-from typing import Any, AsyncIterator, Dict, List, Optional, Tuple, Union
+from typing import Any, AsyncIterator, Dict, List, Optional, Tuple
 from urllib.parse import urlencode, urlsplit
 
 import aiohttp
@@ -38,7 +38,8 @@ log = logging.getLogger("active_monitor_amd.kube.http")
 Obj = Dict[str, Any]
 
 
-def _error_for(status: int, body: str) -> ApiError:
+def _error_for(status: int, raw: bytes) -> ApiError:
+    body = raw.decode("utf-8", "replace")
     reason = ""
     message = body
     details = None
@@ -81,17 +82,8 @@ def _warning_text(header: str) -> str:
     return re.sub(r"\\(.)", r"\1", m.group(1))
 
 
-def _as_text(raw: Union[bytes, str]) -> str:
-    """Response body as text: the pool hands over bytes, aiohttp text."""
-    return raw.decode("utf-8", "replace") if isinstance(raw, bytes) else raw
-
-
-def _decode_body(raw: Union[bytes, str]) -> Obj:
-    if not raw:
-        return {}
-    if isinstance(raw, bytes):
-        return wirecodec.loads_lenient(raw)
-    return json.loads(raw)
+def _fv_params(field_validation: Optional[str]) -> Optional[Dict[str, str]]:
+    return {"fieldValidation": field_validation} if field_validation else None
 
 
 class _Expired(Exception):
@@ -201,13 +193,10 @@ class HttpSubscription:
             params["resourceVersion"] = self._resource_version
         path = self._client._collection_path(self.api_version, self.kind, self.namespace)
         source = self._client._credentials
-        cred: Optional[Credential] = None
-        headers = None
-        if source is not None:
-            cred = await source.get()
-            headers = {"Authorization": f"Bearer {cred.token}"}
+        cred = await source.get() if source is not None else None
         async with self._client._session.get(
-            self._client.base_url + path, params=params, headers=headers,
+            self._client.base_url + path, params=params,
+            headers=self._client._session_auth(cred),
             # sock_read is the client-side safety net behind the server
             # budget: a connection that goes dead-quiet past it is aborted
             # and the reconnect/resume path takes over
@@ -216,13 +205,13 @@ class HttpSubscription:
             ),
         ) as resp:
             if resp.status == 410:
-                await resp.text()
+                await resp.read()
                 raise _Expired()
             if resp.status == 401 and source is not None:
                 source.invalidate(cred)
-                raise _WatchUnauthorized(_error_for(401, await resp.text()))
+                raise _WatchUnauthorized(_error_for(401, await resp.read()))
             if resp.status >= 400:
-                raise _error_for(resp.status, await resp.text())
+                raise _error_for(resp.status, await resp.read())
             self._auth_retry_armed = True
             # incremental framing: newline-delimited JSON without readline's
             # line-length ceiling (a >64 KB Workflow event must not wedge the
@@ -515,57 +504,33 @@ class HttpClient:
     # -- requests -----------------------------------------------------------
 
     async def _request(self, method: str, path: str, body: Optional[Obj] = None,
-                       params: Optional[Dict[str, str]] = None) -> Obj:
+                       params: Optional[Dict[str, str]] = None, *,
+                       content_type: Optional[str] = None,
+                       via_session: bool = False) -> Obj:
+        """Every unary request: rate limit, count, credential, send, map an
+        error status to its exception, decode. With a credential source a 401
+        means the request was not processed, so for any verb: invalidate what
+        was used, fetch a fresh credential, send once more (a request of its
+        own to the limiter and the counter). The second answer stands,
+        whatever it is. A fixed ``token=`` is not retried."""
         if self._session is None:
             raise RuntimeError("HttpClient.start() must be called before requests")
         await self._limiter.acquire()
         self.request_count += 1
-        if self._credentials is not None:
-            return await self._with_credentials(
-                lambda cred: self._send(method, path, body, params, cred)
-            )
-        if self._pool is not None:
-            target = path + ("?" + urlencode(params) if params else "")
-            try:
-                status, text_b = await self._pool.request_json(
-                    method, target, self._pool_headers, body
-                )
-            except (ConnectionError, asyncio.IncompleteReadError, OSError):
-                # stale keep-alive connection: one clean retry on a fresh one
-                status, text_b = await self._pool.request_json(
-                    method, target, self._pool_headers, body
-                )
-            if status >= 400:  # only the error path needs text
-                raise _error_for(status, text_b.decode("utf-8", "replace"))
-            return wirecodec.loads_lenient(text_b) if text_b else {}
-        async with self._session.request(
-            method, self.base_url + path,
-            json=body if body is not None else None, params=params,
-        ) as resp:
-            text = await resp.text()
-            if resp.status >= 400:
-                raise _error_for(resp.status, text)
-            return json.loads(text) if text else {}
-
-    # -- requests with a credential source ----------------------------------
-
-    async def _with_credentials(self, send) -> Obj:
-        """Run ``send(credential) -> (status, text)`` with the source's
-        current credential. A 401 means the request was not processed, so for
-        any verb: invalidate what was used, fetch a fresh credential, send
-        once more. The second answer stands, whatever it is."""
         source = self._credentials
-        cred = await source.get()
-        status, raw = await send(cred)
-        if status == 401:
+        cred = await source.get() if source is not None else None
+        status, raw = await self._send(method, path, body, params, cred,
+                                       content_type, via_session)
+        if status == 401 and source is not None:
             source.invalidate(cred)
             cred = await source.get()
             await self._limiter.acquire()
             self.request_count += 1
-            status, raw = await send(cred)
+            status, raw = await self._send(method, path, body, params, cred,
+                                           content_type, via_session)
         if status >= 400:
-            raise _error_for(status, _as_text(raw))
-        return _decode_body(raw)
+            raise _error_for(status, raw)
+        return wirecodec.loads_lenient(raw) if raw else {}
 
     def _auth_block(self, cred: Credential) -> str:
         if cred is not self._hdr_cred:
@@ -575,61 +540,40 @@ class HttpClient:
             self._hdr_cred = cred
         return self._hdr_block
 
+    @staticmethod
+    def _session_auth(cred: Optional[Credential]) -> Dict[str, str]:
+        """Per-request headers for the aiohttp session; without a source's
+        credential the session's own (a fixed token, or none) stand."""
+        return {} if cred is None else {"Authorization": f"Bearer {cred.token}"}
+
     async def _send(self, method: str, path: str, body: Optional[Obj],
-                    params: Optional[Dict[str, str]],
-                    cred: Credential) -> Tuple[int, Union[bytes, str]]:
-        if self._pool is not None:
+                    params: Optional[Dict[str, str]], cred: Optional[Credential],
+                    content_type: Optional[str],
+                    via_session: bool) -> Tuple[int, bytes]:
+        """One round trip, over the pool, or over the aiohttp session for
+        https targets and for ``via_session`` requests: those set their own
+        Content-Type and have their ``Warning`` response headers collected."""
+        if self._pool is not None and not via_session:
             target = path + ("?" + urlencode(params) if params else "")
-            headers = self._auth_block(cred)
+            headers = self._pool_headers if cred is None else self._auth_block(cred)
             try:
                 return await self._pool.request_json(method, target, headers, body)
             except (ConnectionError, asyncio.IncompleteReadError, OSError):
                 # stale keep-alive connection: one clean retry on a fresh one
                 return await self._pool.request_json(method, target, headers, body)
+        headers = self._session_auth(cred)
+        if content_type:
+            headers["Content-Type"] = content_type
         async with self._session.request(
-            method, self.base_url + path,
-            json=body if body is not None else None, params=params,
-            headers={"Authorization": f"Bearer {cred.token}"},
+            method, self.base_url + path, params=params, headers=headers,
+            data=wirecodec.dumpb(body) if body is not None else None,
         ) as resp:
-            return resp.status, await resp.text()
-
-    async def _send_session(self, method: str, path: str, body: Obj,
-                            content_type: str,
-                            params: Optional[Dict[str, str]],
-                            cred: Optional[Credential]) -> Tuple[int, str]:
-        """One request through the aiohttp session: the path with control
-        over request headers and sight of response headers."""
-        headers = {"Content-Type": content_type}
-        if cred is not None:
-            headers["Authorization"] = f"Bearer {cred.token}"
-        async with self._session.request(
-            method, self.base_url + path, data=wirecodec.dumpb(body),
-            headers=headers, params=params,
-        ) as resp:
-            for value in resp.headers.getall("Warning", ()):
-                text = _warning_text(value)
-                log.warning("apiserver warning: %s", text)
-                self.warnings.append(text)
-            return resp.status, await resp.text()
-
-    async def _request_validated(self, method: str, path: str, body: Obj,
-                                 field_validation: Optional[str],
-                                 content_type: str = "application/json") -> Obj:
-        """A write that names its ``fieldValidation`` (or a patch): off the
-        pooled fast path, through the session."""
-        params = {"fieldValidation": field_validation} if field_validation else None
-        await self._limiter.acquire()
-        self.request_count += 1
-        if self._credentials is not None:
-            return await self._with_credentials(
-                lambda cred: self._send_session(
-                    method, path, body, content_type, params, cred)
-            )
-        status, text = await self._send_session(
-            method, path, body, content_type, params, None)
-        if status >= 400:
-            raise _error_for(status, text)
-        return json.loads(text) if text else {}
+            if via_session:
+                for value in resp.headers.getall("Warning", ()):
+                    text = _warning_text(value)
+                    log.warning("apiserver warning: %s", text)
+                    self.warnings.append(text)
+            return resp.status, await resp.read()
 
     async def get(self, api_version: str, kind: str, namespace: str, name: str,
                   snapshot_read: bool = False) -> Obj:
@@ -664,30 +608,26 @@ class HttpClient:
         path = self._collection_path(
             obj.get("apiVersion", ""), obj.get("kind", ""), meta.get("namespace")
         )
-        if field_validation is not None:
-            return await self._request_validated("POST", path, obj, field_validation)
-        return await self._request("POST", path, obj)
+        return await self._request("POST", path, obj, _fv_params(field_validation),
+                                   via_session=field_validation is not None)
 
-    async def update(self, obj: Obj, field_validation: Optional[str] = None) -> Obj:
+    def _path_of(self, obj: Obj) -> str:
         meta = obj.get("metadata") or {}
-        path = self._object_path(
+        return self._object_path(
             obj.get("apiVersion", ""), obj.get("kind", ""),
             meta.get("namespace", ""), meta.get("name", ""),
         )
-        if field_validation is not None:
-            return await self._request_validated("PUT", path, obj, field_validation)
-        return await self._request("PUT", path, obj)
+
+    async def update(self, obj: Obj, field_validation: Optional[str] = None) -> Obj:
+        return await self._request("PUT", self._path_of(obj), obj,
+                                   _fv_params(field_validation),
+                                   via_session=field_validation is not None)
 
     async def update_status(self, obj: Obj,
                             field_validation: Optional[str] = None) -> Obj:
-        meta = obj.get("metadata") or {}
-        path = self._object_path(
-            obj.get("apiVersion", ""), obj.get("kind", ""),
-            meta.get("namespace", ""), meta.get("name", ""),
-        ) + "/status"
-        if field_validation is not None:
-            return await self._request_validated("PUT", path, obj, field_validation)
-        return await self._request("PUT", path, obj)
+        return await self._request("PUT", self._path_of(obj) + "/status", obj,
+                                   _fv_params(field_validation),
+                                   via_session=field_validation is not None)
 
     async def patch(self, api_version: str, kind: str, namespace: str, name: str,
                     patch: Obj, subresource: str = "",
@@ -697,9 +637,9 @@ class HttpClient:
         path = self._object_path(api_version, kind, namespace, name)
         if subresource:
             path += f"/{subresource}"
-        return await self._request_validated(
-            "PATCH", path, patch, field_validation,
-            content_type="application/merge-patch+json")
+        return await self._request("PATCH", path, patch, _fv_params(field_validation),
+                                   content_type="application/merge-patch+json",
+                                   via_session=True)
 
     async def delete(self, api_version: str, kind: str, namespace: str, name: str) -> None:
         await self._request("DELETE", self._object_path(api_version, kind, namespace, name))

@@ -102,7 +102,7 @@ def parse_label_selector(selector: Optional[str]) -> Dict[str, str]:
     return out
 
 
-def _labels_match(obj: Obj, selector: Dict[str, str]) -> bool:
+def labels_match(obj: Obj, selector: Dict[str, str]) -> bool:
     labels = (obj.get("metadata") or {}).get("labels") or {}
     return all(labels.get(k) == v for k, v in selector.items())
 
@@ -129,7 +129,7 @@ def parse_field_selector(selector: Optional[str]) -> List[Tuple[str, str, bool]]
     return out
 
 
-def _fields_match(obj: Obj, terms: List[Tuple[str, str, bool]]) -> bool:
+def fields_match(obj: Obj, terms: List[Tuple[str, str, bool]]) -> bool:
     for path, want, negated in terms:
         cur: Any = obj
         for seg in path.split("."):
@@ -141,6 +141,22 @@ def _fields_match(obj: Obj, terms: List[Tuple[str, str, bool]]) -> bool:
         if (have == want) == negated:
             return False
     return True
+
+
+def object_rv(obj: Obj, unparsable: int = 0) -> int:
+    """``metadata.resourceVersion`` as a number (0 when there is none)."""
+    try:
+        return int((obj.get("metadata") or {}).get("resourceVersion", 0))
+    except (TypeError, ValueError):
+        return unparsable
+
+
+def _selects(obj: Obj, api_version: str, kind: str, namespace: Optional[str]) -> bool:
+    """Whether a watch of (apiVersion, kind[, namespace]) is told of ``obj``."""
+    if obj.get("apiVersion") != api_version or obj.get("kind") != kind:
+        return False
+    return namespace is None or (
+        (obj.get("metadata") or {}).get("namespace", "") == namespace)
 
 
 class Subscription:
@@ -159,11 +175,7 @@ class Subscription:
     def _offer(self, event: Dict[str, Any]) -> None:
         if self._closed:
             return
-        obj = event["object"]
-        meta = obj.get("metadata") or {}
-        if obj.get("apiVersion") != self.api_version or obj.get("kind") != self.kind:
-            return
-        if self.namespace is not None and meta.get("namespace", "") != self.namespace:
+        if not _selects(event["object"], self.api_version, self.kind, self.namespace):
             return
         try:
             # events carry a shared read-only snapshot (copied once at
@@ -296,10 +308,19 @@ class MemoryApiServer:
 
     # -- admission -----------------------------------------------------------
 
+    def _enter_write(self, api_version: str, kind: str,
+                     field_validation: str) -> Any:
+        """What every write does on entry, before it takes the lock or counts
+        itself, unless the mode is ``"Warn"`` and no schema is installed at
+        all: refuse a wrong mode, whether or not anything would be pruned,
+        and look up the kind's validator (None: stored as given). The write
+        hands its object to :meth:`_admit` once it is named and complete."""
+        if field_validation != "Warn":
+            self._check_mode(field_validation)
+        return self._schemas.get((api_version, kind))
+
     @staticmethod
     def _check_mode(field_validation: str) -> None:
-        """Every write checks its mode on entry: a wrong one is refused
-        whether or not a schema is installed or anything would be pruned."""
         if field_validation not in FIELD_VALIDATION_MODES:
             raise BadRequestError(
                 f'invalid fieldValidation "{field_validation}": supported '
@@ -361,6 +382,22 @@ class MemoryApiServer:
         ns = meta.get("namespace", "") if info.namespaced else ""
         return (obj.get("apiVersion", ""), obj.get("kind", ""), ns, meta.get("name", ""))
 
+    def _resolve(self, api_version: str, kind: str, namespace: str, name: str) -> Key:
+        info = self.registry.by_kind(api_version, kind)
+        return (api_version, kind, namespace if info.namespaced else "", name)
+
+    @staticmethod
+    def _check_fresh(obj: Obj, meta: Obj, ex_meta: Obj) -> None:
+        """Optimistic concurrency: a write that names a resourceVersion must
+        name the stored one."""
+        rv = meta.get("resourceVersion")
+        if rv and str(rv) != str(ex_meta.get("resourceVersion")):
+            raise ConflictError(
+                f'Operation cannot be fulfilled on {obj.get("kind")} '
+                f'"{meta.get("name")}": the object has been modified; please apply '
+                f"your changes to the latest version and try again"
+            )
+
     def _not_found(self, api_version: str, kind: str, name: str) -> NotFoundError:
         info = self.registry.by_kind(api_version, kind)
         group = api_version.split("/")[0] if "/" in api_version else ""
@@ -385,10 +422,7 @@ class MemoryApiServer:
 
     def _publish(self, ev_type: str, obj: Obj) -> None:
         event = {"type": ev_type, "object": obj}
-        try:
-            rv = int((obj.get("metadata") or {}).get("resourceVersion", 0))
-        except (TypeError, ValueError):
-            rv = self._rv
+        rv = object_rv(obj, self._rv)
         if self._journal is not None:
             self._journal_event(ev_type, obj, rv)
         self._history.append((rv, ev_type, obj))
@@ -429,15 +463,8 @@ class MemoryApiServer:
                 )
             out = []
             for rv, ev_type, obj in self._history:
-                if rv <= since:
-                    continue
-                if obj.get("apiVersion") != api_version or obj.get("kind") != kind:
-                    continue
-                if namespace is not None and (obj.get("metadata") or {}).get(
-                    "namespace", ""
-                ) != namespace:
-                    continue
-                out.append({"type": ev_type, "object": obj})
+                if rv > since and _selects(obj, api_version, kind, namespace):
+                    out.append({"type": ev_type, "object": obj})
             return out
 
     def _unsubscribe(self, sub: Subscription) -> None:
@@ -462,8 +489,10 @@ class MemoryApiServer:
         raises :class:`BadRequestError`, ``"Warn"`` appends their paths to
         the ``warnings`` list when one is given, ``"Ignore"`` says nothing.
         Any other mode raises :class:`BadRequestError`, always."""
-        if field_validation != "Warn":
-            self._check_mode(field_validation)
+        validator = None
+        if field_validation != "Warn" or self._schemas:
+            validator = self._enter_write(
+                obj.get("apiVersion", ""), obj.get("kind", ""), field_validation)
         if not transfer:
             obj = deep_copy(obj)
         meta = obj.setdefault("metadata", {})
@@ -483,11 +512,8 @@ class MemoryApiServer:
                     raise AlreadyExistsError(f"could not generate unique name for {gen}")
             # named first, as the apiserver does, so that a refusal can say
             # which object; nothing of the write is visible yet
-            if self._schemas:
-                validator = self._schemas.get(
-                    (obj.get("apiVersion", ""), obj.get("kind", "")))
-                if validator is not None:
-                    self._admit(validator, obj, field_validation, warnings)
+            if validator is not None:
+                self._admit(validator, obj, field_validation, warnings)
             key = self._key(obj)
             if key in self._objects:
                 raise AlreadyExistsError(
@@ -522,11 +548,10 @@ class MemoryApiServer:
         other than metadata/status are shared with the store — callers must
         treat those as read-only (the controller hot path opts in; the default
         is a fully private deep copy, safe to mutate)."""
-        info = self.registry.by_kind(api_version, kind)
-        ns = namespace if info.namespaced else ""
+        key = self._resolve(api_version, kind, namespace, name)
         with self._lock:
             self.op_counts["get"] += 1
-            obj = self._objects.get((api_version, kind, ns, name))
+            obj = self._objects.get(key)
             if obj is None:
                 raise self._not_found(api_version, kind, name)
             return snapshot(obj) if snapshot_read else deep_copy(obj)
@@ -551,19 +576,20 @@ class MemoryApiServer:
                     continue
                 if namespace is not None and ns != namespace:
                     continue
-                if selector and not _labels_match(obj, selector):
+                if selector and not labels_match(obj, selector):
                     continue
-                if fields and not _fields_match(obj, fields):
+                if fields and not fields_match(obj, fields):
                     continue
                 out.append(copier(obj))
             return out
 
     def update(self, obj: Obj, field_validation: str = "Warn",
                warnings: Optional[List[str]] = None) -> Obj:
-        if field_validation != "Warn":
-            self._check_mode(field_validation)
         obj = deep_copy(obj)
         key = self._key(obj)
+        validator = None
+        if field_validation != "Warn" or self._schemas:
+            validator = self._enter_write(key[0], key[1], field_validation)
         meta = obj.setdefault("metadata", {})
         with self._lock:
             self.op_counts["update"] += 1
@@ -571,13 +597,7 @@ class MemoryApiServer:
             if existing is None:
                 raise self._not_found(key[0], key[1], key[3])
             ex_meta = existing["metadata"]
-            rv = meta.get("resourceVersion")
-            if rv and str(rv) != str(ex_meta.get("resourceVersion")):
-                raise ConflictError(
-                    f'Operation cannot be fulfilled on {obj.get("kind")} '
-                    f'"{meta.get("name")}": the object has been modified; please apply '
-                    f"your changes to the latest version and try again"
-                )
+            self._check_fresh(obj, meta, ex_meta)
             # immutable metadata
             meta["uid"] = ex_meta.get("uid")
             meta["creationTimestamp"] = ex_meta.get("creationTimestamp")
@@ -589,10 +609,8 @@ class MemoryApiServer:
                     obj["status"] = deep_copy(existing["status"])
                 else:
                     obj.pop("status", None)
-            if self._schemas:
-                validator = self._schemas.get((key[0], key[1]))
-                if validator is not None:
-                    self._admit(validator, obj, field_validation, warnings)
+            if validator is not None:
+                self._admit(validator, obj, field_validation, warnings)
             # no-op updates don't bump the resourceVersion or emit watch
             # events (apiserver semantics — prevents self-triggering loops)
             meta["resourceVersion"] = ex_meta.get("resourceVersion")
@@ -601,18 +619,14 @@ class MemoryApiServer:
                 return deep_copy(existing)
             if obj.get("spec") != existing.get("spec"):
                 meta["generation"] = int(ex_meta.get("generation", 1)) + 1
-            else:
-                meta["generation"] = ex_meta.get("generation", 1)
             meta["resourceVersion"] = self._next_rv()
             self._unindex_owners(key, existing)
             self._objects[key] = obj
             self._index_owners(key, obj)
             # finalizer removal completes a pending delete
             if meta.get("deletionTimestamp") and not meta.get("finalizers"):
-                del self._objects[key]
-                self._unindex_owners(key, obj)
-                self._publish("DELETED", snapshot(obj))
-                self._cascade_delete(meta.get("uid"))
+                # its DELETED carries the rv this update has just assigned
+                self._remove(key, obj, bump_rv=False)
                 return deep_copy(obj)
             self._publish("MODIFIED", snapshot(obj))
             out = deep_copy(obj)
@@ -620,29 +634,21 @@ class MemoryApiServer:
 
     def update_status(self, obj: Obj, field_validation: str = "Warn",
                       warnings: Optional[List[str]] = None) -> Obj:
-        if field_validation != "Warn":
-            self._check_mode(field_validation)
         obj = deep_copy(obj)
         key = self._key(obj)
+        validator = None
+        if field_validation != "Warn" or self._schemas:
+            validator = self._enter_write(key[0], key[1], field_validation)
         meta = obj.get("metadata") or {}
         with self._lock:
             self.op_counts["update_status"] += 1
             existing = self._objects.get(key)
             if existing is None:
                 raise self._not_found(key[0], key[1], key[3])
-            ex_meta = existing["metadata"]
-            rv = meta.get("resourceVersion")
-            if rv and str(rv) != str(ex_meta.get("resourceVersion")):
-                raise ConflictError(
-                    f'Operation cannot be fulfilled on {obj.get("kind")} '
-                    f'"{meta.get("name")}": the object has been modified; please apply '
-                    f"your changes to the latest version and try again"
-                )
-            if self._schemas:
-                validator = self._schemas.get((key[0], key[1]))
-                if validator is not None:
-                    self._admit(validator, obj, field_validation, warnings,
-                                subtree="status")
+            self._check_fresh(obj, meta, existing["metadata"])
+            if validator is not None:
+                self._admit(validator, obj, field_validation, warnings,
+                            subtree="status")
             updated = snapshot(existing)
             if "status" in obj:
                 updated["status"] = deep_copy(obj["status"])
@@ -681,11 +687,11 @@ class MemoryApiServer:
         absent (server-side-apply shape). With a schema installed it is the
         merged result that is validated, not the patch."""
         if field_validation != "Warn":
-            self._check_mode(field_validation)
-        info = self.registry.by_kind(api_version, kind)
-        ns = namespace if info.namespaced else ""
+            self._enter_write(api_version, kind, field_validation)
+        key = self._resolve(api_version, kind, namespace, name)
+        namespaced = self.registry.by_kind(api_version, kind).namespaced
         with self._lock:
-            existing = self._objects.get((api_version, kind, ns, name))
+            existing = self._objects.get(key)
             if existing is None:
                 if not upsert:
                     raise self._not_found(api_version, kind, name)
@@ -694,7 +700,7 @@ class MemoryApiServer:
                 obj.setdefault("kind", kind)
                 meta = obj.setdefault("metadata", {})
                 meta.setdefault("name", name)
-                if info.namespaced:
+                if namespaced:
                     meta.setdefault("namespace", namespace)
                 return self.create(obj, transfer=True,
                                    field_validation=field_validation,
@@ -711,8 +717,8 @@ class MemoryApiServer:
             merged["apiVersion"], merged["kind"] = api_version, kind
             m = merged.setdefault("metadata", {})
             m["name"], m["uid"] = name, existing["metadata"].get("uid")
-            if info.namespaced:
-                m["namespace"] = ns
+            if namespaced:
+                m["namespace"] = key[2]
             # honor an explicit rv in the patch (optimistic concurrency);
             # otherwise patch applies to the current version
             if "resourceVersion" not in (patch_obj.get("metadata") or {}):
@@ -720,11 +726,9 @@ class MemoryApiServer:
             return self.update(merged, field_validation, warnings)
 
     def delete(self, api_version: str, kind: str, namespace: str, name: str) -> None:
-        info = self.registry.by_kind(api_version, kind)
-        ns = namespace if info.namespaced else ""
+        key = self._resolve(api_version, kind, namespace, name)
         with self._lock:
             self.op_counts["delete"] += 1
-            key = (api_version, kind, ns, name)
             obj = self._objects.get(key)
             if obj is None:
                 raise self._not_found(api_version, kind, name)
@@ -735,29 +739,28 @@ class MemoryApiServer:
                     meta["resourceVersion"] = self._next_rv()
                     self._publish("MODIFIED", snapshot(obj))
                 return
-            del self._objects[key]
-            self._unindex_owners(key, obj)
+            self._remove(key, obj)
+
+    def _remove(self, key: Key, obj: Obj, bump_rv: bool = True) -> None:
+        """Take ``obj`` out of the store and tell the watchers, then do the
+        same for its dependents — background-propagation GC: objects whose
+        ownerReferences name the deleted uid (the mechanism behind Workflow
+        cleanup on HealthCheck delete, healthcheck_controller.go:512-522).
+        O(dependents) via the owner-uid index, not a store scan."""
+        del self._objects[key]
+        self._unindex_owners(key, obj)
+        meta = obj["metadata"]
+        if bump_rv:
             # deletion bumps the rv (apiserver semantics) so a watch resuming
             # from just before the delete replays the DELETED event
             meta["resourceVersion"] = self._next_rv()
-            self._publish("DELETED", snapshot(obj))
-            self._cascade_delete(meta.get("uid"))
-
-    def _cascade_delete(self, owner_uid: Optional[str]) -> None:
-        """Background-propagation GC: delete dependents whose ownerReferences
-        name the deleted uid (the mechanism behind Workflow cleanup on
-        HealthCheck delete, healthcheck_controller.go:512-522). O(dependents)
-        via the owner-uid index, not a store scan."""
-        if not owner_uid:
-            return
-        dependents = list(self._by_owner.pop(owner_uid, ()))
-        for key in dependents:
-            obj = self._objects.pop(key, None)
-            if obj is not None:
-                self._unindex_owners(key, obj)
-                obj["metadata"]["resourceVersion"] = self._next_rv()
-                self._publish("DELETED", snapshot(obj))
-                self._cascade_delete(obj["metadata"].get("uid"))
+        self._publish("DELETED", snapshot(obj))
+        uid = meta.get("uid")
+        if uid:
+            for dep_key in list(self._by_owner.pop(uid, ())):
+                dependent = self._objects.get(dep_key)
+                if dependent is not None:
+                    self._remove(dep_key, dependent)
 
     def resource_version(self) -> str:
         """The store's current global resourceVersion (list metadata rv)."""

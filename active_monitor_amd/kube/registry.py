@@ -7,7 +7,7 @@ api/v1alpha1/groupversion_info.go:26-35) plus the Argo GVK/GVR constants
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, Tuple
+from typing import Dict, ItemsView, Tuple
 
 from .. import API_VERSION
 
@@ -53,6 +53,10 @@ class Registry:
     def register(self, info: ResourceInfo) -> None:
         self._by_kind[(info.api_version, info.kind)] = info
         self._by_plural[(info.api_version, info.plural)] = info
+
+    def kinds(self) -> ItemsView[Tuple[str, str], ResourceInfo]:
+        """``((api_version, kind), info)`` of every registered kind."""
+        return self._by_kind.items()
 
     def by_kind(self, api_version: str, kind: str) -> ResourceInfo:
         info = self._by_kind.get((api_version, kind))

@@ -19,12 +19,19 @@ from __future__ import annotations
 import asyncio
 import hmac
 import logging
-from typing import Optional, Set, Tuple
+from typing import List, Optional, Set, Tuple
 
 from ..utils import wirecodec
 from ..utils.wirecodec import EXPECT_CONTINUE, WANT_TABLE
 from .errors import ApiError, ExpiredError, InvalidError, UnauthorizedError
-from .memory import MemoryApiServer
+from .memory import (
+    MemoryApiServer,
+    fields_match,
+    labels_match,
+    object_rv,
+    parse_field_selector,
+    parse_label_selector,
+)
 
 log = logging.getLogger("active_monitor_amd.kube.server")
 
@@ -72,6 +79,36 @@ def _status_body(err: ApiError) -> dict:
     if details:  # a schema rejection: name, group, kind and the causes
         body["details"] = details
     return body
+
+
+def _failure(err: ApiError, status: Optional[int] = None) -> Tuple[int, dict]:
+    """``(status, Status body)`` of a refusal; the HTTP status is the error's
+    own code unless the route gives it another."""
+    return status or err.code, _status_body(err)
+
+
+def _route(path: str) -> Optional[Tuple[str, str, str, str, str]]:
+    """``(api_version, namespace, plural, name, subresource)`` of a resource
+    path, ``""`` for what it does not name; None for any other path.
+
+        /api/v1/...  or  /apis/{group}/{version}/...  followed by
+        {plural}[/{name}[/{subresource}]]
+        namespaces/{ns}/{plural}[/{name}[/{subresource}]]
+
+    ``namespaces/{ns}`` is a namespace prefix only with a plural after it:
+    /api/v1/namespaces[/{name}] is the Namespace resource itself."""
+    segs = [seg for seg in path.split("/") if seg]
+    if len(segs) >= 2 and segs[0] == "api":
+        api_version, parts = segs[1], segs[2:]
+    elif len(segs) >= 3 and segs[0] == "apis":
+        api_version, parts = f"{segs[1]}/{segs[2]}", segs[3:]
+    else:
+        return None
+    namespace = ""
+    if len(parts) >= 3 and parts[0] == "namespaces":
+        namespace, parts = parts[1], parts[2:]
+    plural, name, subresource = (parts + ["", "", ""])[:3]
+    return api_version, namespace, plural, name, subresource
 
 
 class _Warned:
@@ -213,11 +250,11 @@ class ApiServerFrontend:
                 if (flags & WANT_TABLE and method == "GET" and status == 200
                         and isinstance(obj, dict)):
                     obj = self._to_table(obj)
-                if type(obj) is dict:
+                if type(obj) is dict or not isinstance(obj, (_Warned, str)):
                     writer.write(wirecodec.frame(_json_prefix(status), obj))
                 elif isinstance(obj, _Warned):
                     writer.write(wirecodec.frame(obj.prefix(status), obj.obj))
-                elif isinstance(obj, str):  # health probes are plain text
+                else:  # health probes are plain text
                     payload = obj.encode()
                     writer.write(
                         (
@@ -226,8 +263,6 @@ class ApiServerFrontend:
                             f"Content-Length: {len(payload)}\r\n\r\n"
                         ).encode("latin-1") + payload
                     )
-                else:
-                    writer.write(wirecodec.frame(_json_prefix(status), obj))
                 await writer.drain()
         except (ConnectionError, asyncio.IncompleteReadError,
                 asyncio.LimitOverrunError, asyncio.CancelledError):
@@ -242,18 +277,6 @@ class ApiServerFrontend:
                 pass
 
     # -- routing ------------------------------------------------------------
-
-    def _split(self, path: str) -> Optional[Tuple[str, str]]:
-        """Return (api_version, tail) for /api/v1/... or /apis/g/v/...; None
-        for non-resource paths."""
-        segs = [s for s in path.split("/") if s]
-        if not segs:
-            return None
-        if segs[0] == "api" and len(segs) >= 2:
-            return segs[1], "/".join(segs[2:])
-        if segs[0] == "apis" and len(segs) >= 3:
-            return f"{segs[1]}/{segs[2]}", "/".join(segs[3:])
-        return None
 
     def _serve_unary(self, method: str, path: str, query: dict,
                      body: bytes, content_type: str = "") -> Tuple[int, Optional[dict]]:
@@ -271,17 +294,16 @@ class ApiServerFrontend:
             }
         if path in ("/healthz", "/readyz", "/livez"):
             return 200, "ok"  # apiserver health probes (kubectl checks these)
-        split = self._split(path)
-        if split is None:
-            return 404, _status_body(ApiError(f"the server could not find {path}"))
-        api_version, tail = split
-        if not tail:  # /api/v1 or /apis/g/v → resource discovery
-            return 200, self._resource_list(api_version)
-        return self._dispatch(method, api_version, tail, query, body, content_type)
+        route = _route(path)
+        if route is None:
+            return _failure(ApiError(f"the server could not find {path}"), 404)
+        if not route[2]:  # /api/v1 or /apis/g/v → resource discovery
+            return 200, self._resource_list(route[0])
+        return self._dispatch(method, route, query, body, content_type)
 
     def _discovery_apis(self) -> dict:
         groups_map: dict = {}
-        for (av, _), info in self.server.registry._by_kind.items():
+        for (av, _), info in self.server.registry.kinds():
             if "/" in av:
                 g, v = av.split("/", 1)
                 groups_map.setdefault(g, set()).add(v)
@@ -297,7 +319,7 @@ class ApiServerFrontend:
 
     def _resource_list(self, api_version: str) -> dict:
         resources = []
-        for (av, kind), info in sorted(self.server.registry._by_kind.items()):
+        for (av, kind), info in sorted(self.server.registry.kinds()):
             if av != api_version:
                 continue
             resources.append({
@@ -319,27 +341,14 @@ class ApiServerFrontend:
         return {"kind": "APIResourceList", "apiVersion": "v1",
                 "groupVersion": api_version, "resources": resources}
 
-    def _dispatch(self, method: str, api_version: str, tail: str, query: dict,
-                  body: bytes, content_type: str = "") -> Tuple[int, Optional[dict]]:
-        # tail forms:
-        #   {plural}[/{name}[/status]]
-        #   namespaces/{ns}/{plural}[/{name}[/status]]
-        parts = [p for p in tail.split("/") if p]
-        namespace = ""
-        # /api/v1/namespaces/{ns}/{plural}... is namespaced access;
-        # /api/v1/namespaces[/{name}] (≤2 segments) is the Namespace resource
-        if len(parts) >= 3 and parts[0] == "namespaces":
-            namespace = parts[1]
-            parts = parts[2:]
-        plural = parts[0] if parts else ""
-        name = parts[1] if len(parts) > 1 else ""
-        subresource = parts[2] if len(parts) > 2 else ""
-
+    def _dispatch(self, method: str, route: Tuple[str, str, str, str, str],
+                  query: dict, body: bytes,
+                  content_type: str = "") -> Tuple[int, Optional[dict]]:
+        api_version, namespace, plural, name, subresource = route
         try:
-            info = self.server.registry.by_plural(api_version, plural)
+            kind = self.server.registry.by_plural(api_version, plural).kind
         except KeyError:
-            return 404, _status_body(ApiError(f"unknown resource {plural}"))
-        kind = info.kind
+            return _failure(ApiError(f"unknown resource {plural}"), 404)
 
         try:
             if method == "GET" and not name:
@@ -387,9 +396,9 @@ class ApiServerFrontend:
                 if ct == "application/json-patch+json":
                     # RFC 6902 op lists are not supported; kubectl defaults
                     # to strategic/merge for CRDs anyway
-                    return 415, _status_body(
-                        InvalidError("json-patch is not supported; use merge-patch")
-                    )
+                    return _failure(
+                        InvalidError("json-patch is not supported; use merge-patch"),
+                        415)
                 if ct == "application/apply-patch+yaml":
                     import yaml as _yaml
 
@@ -409,11 +418,11 @@ class ApiServerFrontend:
                     subresource=subresource, upsert=upsert,
                 )
         except InvalidError as e:
-            code = 400 if e.message == "request body is not valid JSON" else e.code
-            return code, _status_body(e)
+            return _failure(
+                e, 400 if e.message == "request body is not valid JSON" else None)
         except ApiError as e:
-            return e.code, _status_body(e)
-        return 405, _status_body(ApiError(f"unsupported method {method}"))
+            return _failure(e)
+        return _failure(ApiError(f"unsupported method {method}"), 405)
 
     @staticmethod
     def _write(status: int, query: dict, write, *args, **kwargs):
@@ -506,12 +515,11 @@ class ApiServerFrontend:
     # -- watch --------------------------------------------------------------
 
     @staticmethod
-    def _ev_rv(ev: dict) -> int:
-        try:
-            return int(((ev.get("object") or {}).get("metadata") or {})
-                       .get("resourceVersion", 0))
-        except (TypeError, ValueError):
-            return 0
+    async def _refuse_watch(writer: asyncio.StreamWriter, err: ApiError,
+                            status: int) -> None:
+        status, body = _failure(err, status)
+        writer.write(wirecodec.frame(_json_prefix(status), body))
+        await writer.drain()
 
     async def _serve_watch(self, writer: asyncio.StreamWriter, path: str,
                            query: dict) -> None:
@@ -521,44 +529,32 @@ class ApiServerFrontend:
         ADDED. The live subscription is opened before the replay snapshot is
         taken and overlap is deduplicated by rv, so no event can fall between
         replay and stream. Framing: Connection: close (read-until-EOF)."""
-        split = self._split(path)
-        err = None
-        if split is None:
-            err = ApiError(f"the server could not find {path}")
-        else:
-            api_version, tail = split
-            parts = [p for p in tail.split("/") if p]
-            namespace = None
-            if len(parts) >= 2 and parts[0] == "namespaces":
-                namespace = parts[1]
-                parts = parts[2:]
-            try:
-                info = self.server.registry.by_plural(api_version, parts[0] if parts else "")
-            except KeyError:
-                err = ApiError(f"unknown resource {tail}")
-        if err is not None:
-            writer.write(wirecodec.frame(_json_prefix(404), _status_body(err)))
-            await writer.drain()
-            return
-        kind = info.kind
+        route = _route(path)
+        if route is None:
+            return await self._refuse_watch(
+                writer, ApiError(f"the server could not find {path}"), 404)
+        api_version, namespace, plural = route[:3]  # a name is not looked at
+        namespace = namespace or None
+        try:
+            kind = self.server.registry.by_plural(api_version, plural).kind
+        except KeyError:
+            # a watch names all that follows the version, not the plural alone
+            tail = [seg for seg in path.split("/") if seg][api_version.count("/") + 2:]
+            return await self._refuse_watch(
+                writer, ApiError("unknown resource " + "/".join(tail)), 404)
 
         rv_param = query.get("resourceVersion")
-        selector = {}
-        fields = []
-        if query.get("labelSelector"):
-            from .memory import parse_label_selector
-
-            try:
-                selector = parse_label_selector(query["labelSelector"])
-            except ApiError:
-                selector = {}
-        if query.get("fieldSelector"):
-            from .memory import parse_field_selector
-
-            try:
-                fields = parse_field_selector(query["fieldSelector"])
-            except ApiError:
-                fields = []
+        # a selector that does not parse leaves the watch unfiltered
+        selector: dict = {}
+        fields: List[tuple] = []
+        try:
+            selector = parse_label_selector(query.get("labelSelector"))
+        except ApiError:
+            pass
+        try:
+            fields = parse_field_selector(query.get("fieldSelector"))
+        except ApiError:
+            pass
         sub = self.server.watch(api_version, kind, namespace)
         self._live_subs.append(sub)
         try:
@@ -568,9 +564,7 @@ class ApiServerFrontend:
                 try:
                     replay = self.server.events_since(api_version, kind, namespace, rv_param)
                 except ExpiredError as e:
-                    writer.write(wirecodec.frame(_json_prefix(410), _status_body(e)))
-                    await writer.drain()
-                    return
+                    return await self._refuse_watch(writer, e, 410)
                 try:
                     last_rv = int(rv_param)
                 except ValueError:
@@ -586,17 +580,16 @@ class ApiServerFrontend:
                 b"Content-Type: application/json;stream=watch\r\n"
                 b"Connection: close\r\n\r\n"
             )
-            from .memory import _fields_match, _labels_match
 
             def _matches(obj: dict) -> bool:
-                if selector and not _labels_match(obj, selector):
+                if selector and not labels_match(obj, selector):
                     return False
-                if fields and not _fields_match(obj, fields):
+                if fields and not fields_match(obj, fields):
                     return False
                 return True
 
             for ev in replay:
-                last_rv = max(last_rv, self._ev_rv(ev))
+                last_rv = max(last_rv, object_rv(ev.get("object") or {}))
                 if not _matches(ev.get("object") or {}):
                     continue
                 writer.write(wirecodec.dumpb(ev) + b"\n")
@@ -616,7 +609,7 @@ class ApiServerFrontend:
                     pass
             try:
                 async for ev in sub:
-                    if self._ev_rv(ev) <= last_rv:
+                    if object_rv(ev.get("object") or {}) <= last_rv:
                         continue  # already covered by the replay snapshot
                     if not _matches(ev.get("object") or {}):
                         continue

@@ -1,6 +1,7 @@
 """HTTP layer tests: HttpClient against the ApiServerFrontend — the full-loop
 equivalent of running against a real kube-apiserver."""
 import asyncio
+import json
 
 import pytest
 
@@ -254,5 +255,138 @@ def test_table_responses_for_kubectl_get(run):
                 async with s.get(base) as r:
                     plain = await r.json()
                 assert plain["kind"] == "HealthCheckList"
+
+    run(go(), timeout=30)
+
+
+# -- the route table, over a raw socket ----------------------------------------
+
+async def raw_get(frontend, target, accept=None):
+    """(status, decoded body) of one GET: a JSON object for a unary answer,
+    the list of watch events for a stream (read until the server closes)."""
+    reader, writer = await asyncio.open_connection(frontend.host, frontend.port)
+    try:
+        writer.write((f"GET {target} HTTP/1.1\r\nHost: test\r\n"
+                      + (f"Accept: {accept}\r\n" if accept else "")
+                      + "\r\n").encode())
+        await writer.drain()
+        head = (await reader.readuntil(b"\r\n\r\n")).decode("latin-1")
+        status = int(head.split(" ", 2)[1])
+        length = [line.split(":", 1)[1] for line in head.split("\r\n")
+                  if line.lower().startswith("content-length:")]
+        if length:
+            return status, json.loads(await reader.readexactly(int(length[0])))
+        assert "stream=watch" in head and "Connection: close" in head
+        lines = (await reader.read()).split(b"\n")
+        return status, [json.loads(line) for line in lines if line]
+    finally:
+        writer.close()
+
+
+def told(answer):
+    """What a row of the route table pins of an answer: the status, and the
+    Status message, or the kind served, or the watch events' objects."""
+    status, body = answer
+    if isinstance(body, list):
+        return status, [(ev["type"], ev["object"]["kind"],
+                         ev["object"]["metadata"]["name"]) for ev in body]
+    if body.get("kind") == "Status":
+        return status, body["message"]
+    return status, body.get("kind")
+
+
+CM_X = ("ADDED", "ConfigMap", "n")
+CM_Y = ("ADDED", "ConfigMap", "m")
+NS_X = ("ADDED", "Namespace", "x")
+GROUP = "/apis/activemonitor.keikoproj.io/v1alpha1"
+
+#: path → (plain GET, the same with ?watch=true)
+ROUTES = [
+    ("/nope", (404, "the server could not find /nope"),
+     (404, "the server could not find /nope")),
+    ("/api/v1/nope", (404, "unknown resource nope"), (404, "unknown resource nope")),
+    (GROUP + "/nope", (404, "unknown resource nope"), (404, "unknown resource nope")),
+    (GROUP + "/namespaces/x/nope/n", (404, "unknown resource nope"),
+     (404, "unknown resource namespaces/x/nope/n")),
+    ("/api/v1/namespaces", (200, "NamespaceList"), (200, [NS_X])),
+    # a watch looks at no name: this is the watch of Namespaces
+    ("/api/v1/namespaces/x", (200, "Namespace"), (200, [NS_X])),
+    ("/api/v1/namespaces/x/configmaps", (200, "ConfigMapList"), (200, [CM_X])),
+    ("/api/v1/namespaces/x/configmaps/n", (200, "ConfigMap"), (200, [CM_X])),
+    ("/api/v1/namespaces/x/configmaps/n/status", (200, "ConfigMap"), (200, [CM_X])),
+    ("/api/v1/configmaps", (200, "ConfigMapList"), (200, [CM_X, CM_Y])),
+    ("/api/v1/namespaces/x/configmaps/absent", (404, 'configmaps "absent" not found'),
+     (200, [CM_X])),
+]
+
+
+class RouteEnv(HttpEnv):
+    async def __aenter__(self):
+        await self.frontend.start()
+        self.client = None
+        self.server.create({"apiVersion": "v1", "kind": "Namespace",
+                            "metadata": {"name": "x"}})
+        for ns, name, tier in (("x", "n", "1"), ("y", "m", "2")):
+            self.server.create({
+                "apiVersion": "v1", "kind": "ConfigMap",
+                "metadata": {"name": name, "namespace": ns, "labels": {"tier": tier}}})
+        return self
+
+    async def __aexit__(self, *exc):
+        await self.frontend.stop()
+
+
+@pytest.mark.parametrize("path,plain,watched", ROUTES, ids=[r[0] for r in ROUTES])
+def test_route_table(run, path, plain, watched):
+    async def go():
+        async with RouteEnv() as env:
+            assert told(await raw_get(env.frontend, path)) == plain
+            assert told(await raw_get(
+                env.frontend, path + "?watch=true&timeoutSeconds=0.2")) == watched
+
+    run(go(), timeout=30)
+
+
+def test_a_selector_that_does_not_parse(run):
+    """A list refuses it with 422; a watch is served unfiltered."""
+    async def go():
+        async with RouteEnv() as env:
+            for param, message in (
+                ("labelSelector=tier", "unsupported selector term: 'tier'"),
+                ("fieldSelector=metadata.name",
+                 "unsupported field selector term: 'metadata.name'"),
+            ):
+                assert told(await raw_get(
+                    env.frontend, f"/api/v1/configmaps?{param}")) == (422, message)
+                assert told(await raw_get(
+                    env.frontend,
+                    f"/api/v1/configmaps?watch=true&timeoutSeconds=0.2&{param}",
+                )) == (200, [CM_X, CM_Y])
+            # and one that does parse filters both
+            for param in ("labelSelector=tier%3D2", "fieldSelector=metadata.name%3Dm"):
+                status, body = await raw_get(env.frontend, f"/api/v1/configmaps?{param}")
+                assert [o["metadata"]["name"] for o in body["items"]] == ["m"]
+                assert told(await raw_get(
+                    env.frontend,
+                    f"/api/v1/configmaps?watch=true&timeoutSeconds=0.2&{param}",
+                )) == (200, [CM_Y])
+
+    run(go(), timeout=30)
+
+
+def test_a_404_passes_through_a_table_request(run):
+    async def go():
+        async with RouteEnv() as env:
+            accept = "application/json;as=Table;v=v1;g=meta.k8s.io, application/json"
+            status, body = await raw_get(
+                env.frontend, "/api/v1/namespaces/x/configmaps/absent", accept)
+            assert status == 404
+            assert body == {
+                "kind": "Status", "apiVersion": "v1", "status": "Failure",
+                "message": 'configmaps "absent" not found', "reason": "NotFound",
+                "code": 404}
+            status, body = await raw_get(
+                env.frontend, "/api/v1/namespaces/x/configmaps/n", accept)
+            assert (status, body["kind"]) == (200, "Table")
 
     run(go(), timeout=30)
