@@ -19,7 +19,6 @@ from __future__ import annotations
 import argparse
 import asyncio
 import logging
-import signal
 import sys
 from typing import Optional, Tuple
 
@@ -114,22 +113,19 @@ def build_parser() -> argparse.ArgumentParser:
 async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
     """Process main loop; runs until SIGINT/SIGTERM (or ``stop_event`` for
     tests — the reference covers run()'s error/shutdown paths the same way,
-    cmd/main_test.go:35-64)."""
-    return await _run(args, stop_event)
-
-
-async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
-    if getattr(args, "gc_threshold", 0):
+    cmd/main_test.go:35-64). ``args`` comes from ``build_parser()``."""
+    if args.gc_threshold:
         import gc
 
         gc.set_threshold(args.gc_threshold, 50, 50)
+    # looked up when called, not at import: tests substitute the Manager
     from ..engine import Manager
-    from ..kube import MemoryApiServer, MemoryClient
+    from ..kube.standalone import build_engine, open_store, stop_on_signals
 
     level = {"debug": logging.DEBUG, "info": logging.INFO,
              "warn": logging.WARNING, "error": logging.ERROR}.get(
         args.zap_log_level, logging.INFO)
-    if getattr(args, "log_format", "console") == "json":
+    if args.log_format == "json":
         from .logfmt import JsonFormatter
 
         handler = logging.StreamHandler()
@@ -142,14 +138,14 @@ async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         )
     log = logging.getLogger("active_monitor_amd.main")
 
-    engine = None
+    store = engine = frontend = None  # the memory backend's three parts
     if args.backend == "http":
         from ..kube.config import get_config
 
         cfg = get_config(
             server=args.server, token=args.token,
             insecure=args.insecure_skip_tls_verify, kubeconfig=args.kubeconfig,
-            token_file=getattr(args, "token_file", None),
+            token_file=args.token_file,
         )
         client = cfg.make_client()
         await client.start()
@@ -160,48 +156,32 @@ async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
             await client.close()
             return 1
     else:
-        from ..kube.standalone import standalone_schemas
+        from ..kube import MemoryClient
 
-        schemas, schema_line = standalone_schemas(
-            getattr(args, "schema_validation", True))
-        log.info(schema_line)
-        data_dir = getattr(args, "data_dir", None)
-        if data_dir:
-            from ..kube.persist import StoreError
-
-            try:
-                store = MemoryApiServer.open(data_dir, schemas=schemas)
-            except (StoreError, OSError) as e:
-                log.error("cannot open data directory: %s", e)
-                return 1
-            log.info("data directory %s: loaded %d objects, resourceVersion %s",
-                     store.data_dir, len(store), store.resource_version())
-        else:
-            store = MemoryApiServer(schemas=schemas)
+        store = open_store(args.data_dir, args.schema_validation, log.info, log.error)
+        if store is None:
+            return 1
         client = MemoryClient(store)
-        if args.workflow_engine == "local":
-            from ..workflow import LocalWorkflowEngine
-
-            engine = LocalWorkflowEngine(client, args.namespace,
-                                         recover=bool(data_dir))
+        engine = build_engine(args.workflow_engine, client, args.data_dir,
+                              namespace=args.namespace)
         if args.serve_api:
             from ..kube.server import ApiServerFrontend
 
             addr = parse_bind_address(args.serve_api)
-            frontend = ApiServerFrontend(client.server, addr[0], addr[1])
+            frontend = ApiServerFrontend(store, addr[0], addr[1])
             await frontend.start()
             log.info("serving Kubernetes REST API at %s", frontend.url)
 
     metrics_addr = parse_bind_address(args.metrics_bind_address)
     metrics_security = None
-    if metrics_addr is not None and getattr(args, "metrics_secure", False):
+    if metrics_addr is not None and args.metrics_secure:
         from ..engine.endpoints import build_metrics_security
 
         metrics_security = build_metrics_security(
             True,
-            cert=getattr(args, "metrics_cert", None),
-            key=getattr(args, "metrics_key", None),
-            token_file=getattr(args, "metrics_auth_token_file", None),
+            cert=args.metrics_cert,
+            key=args.metrics_key,
+            token_file=args.metrics_auth_token_file,
         )
 
     manager = Manager(
@@ -213,20 +193,13 @@ async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         leader_elect=args.leader_elect,
         shard_index=args.shard_index,
         shard_count=args.shard_count,
-        shard_ha=getattr(args, "shard_ha", False),
-        shard_lease_duration=getattr(args, "shard_lease_duration", 15.0),
-        shard_renew_interval=getattr(args, "shard_renew_interval", 5.0),
+        shard_ha=args.shard_ha,
+        shard_lease_duration=args.shard_lease_duration,
+        shard_renew_interval=args.shard_renew_interval,
         metrics_security=metrics_security,
     )
 
-    stop = stop_event if stop_event is not None else asyncio.Event()
-    loop = asyncio.get_running_loop()
-    for sig in (signal.SIGINT, signal.SIGTERM):
-        try:
-            loop.add_signal_handler(sig, stop.set)
-        except (NotImplementedError, RuntimeError):  # pragma: no cover - non-unix
-            pass
-
+    stop = stop_on_signals(stop_event if stop_event is not None else asyncio.Event())
     if engine is not None:
         await engine.start()
     await manager.start()
@@ -247,15 +220,17 @@ async def _run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         log.error("manager fatal: %s", manager.fatal_reason)
         rc = 1
     log.info("shutting down")
+    # in order: the controller, what runs its workflows, then its apiserver —
+    # the REST frontend and the store of the memory backend, or the connection
     await manager.stop()
     if engine is not None:
         await engine.stop()
-    if args.backend == "http":
-        await client.close()
-    if args.backend == "memory" and args.serve_api:
+    if frontend is not None:
         await frontend.stop()
-    if args.backend == "memory":
-        client.server.close()
+    if store is not None:
+        store.close()
+    else:
+        await client.close()
     return rc
 
 

@@ -8,14 +8,12 @@ from __future__ import annotations
 
 import asyncio
 import logging
-import time
-from ..api.types import k8s_now, parse_k8s_time
+import os
+
 from ..kube.client import KubeClient
-from ..kube.errors import AlreadyExistsError, ConflictError, NotFoundError
+from .lease import KEEP, Lease
 
 log = logging.getLogger("active_monitor_amd.leader")
-
-LEASE_API_VERSION = "coordination.k8s.io/v1"
 
 
 class LeaderElector:
@@ -29,8 +27,6 @@ class LeaderElector:
         renew_interval: float = 5.0,
         retry_interval: float = 2.0,
     ):
-        import os
-
         # ops/test override for failover latency (mirrors controller-runtime's
         # LeaseDuration/RenewDeadline tunables the reference inherits)
         env_lease = os.environ.get("AM_LEADER_LEASE_SECS")
@@ -49,41 +45,27 @@ class LeaderElector:
         self.retry_interval = retry_interval
         self.is_leader = False
 
-    def _lease_obj(self) -> dict:
-        return {
-            "apiVersion": LEASE_API_VERSION,
-            "kind": "Lease",
-            "metadata": {"name": self.name, "namespace": self.namespace},
-            "spec": {
-                "holderIdentity": self.identity,
-                "leaseDurationSeconds": int(self.lease_duration),
-                "renewTime": k8s_now(),
-            },
-        }
+    def _lease(self) -> Lease:
+        # built per action, not in __init__: lease_duration may be set on the
+        # elector after construction and must be the one in force
+        return Lease(self.client, self.namespace, self.name, self.identity,
+                     self.lease_duration)
 
     async def try_acquire(self) -> bool:
-        try:
-            lease = await self.client.get(LEASE_API_VERSION, "Lease", self.namespace, self.name)
-        except NotFoundError:
-            try:
-                await self.client.create(self._lease_obj())
-                self.is_leader = True
-                return True
-            except AlreadyExistsError:
+        handle = self._lease()
+        lease = await handle.read()
+        if lease is None:
+            ok = await handle.create()
+        else:
+            spec = lease.get("spec") or {}
+            holder = spec.get("holderIdentity")
+            expired = handle.expired(spec)  # exactly lease_duration, no pad
+            if holder and holder != self.identity and not expired:
                 return False
-        spec = lease.get("spec") or {}
-        holder = spec.get("holderIdentity")
-        renew = parse_k8s_time(spec.get("renewTime"))
-        expired = renew is None or (time.time() - renew.timestamp()) > self.lease_duration
-        if holder == self.identity or expired or not holder:
-            lease["spec"] = self._lease_obj()["spec"]
-            try:
-                await self.client.update(lease)
-                self.is_leader = True
-                return True
-            except (ConflictError, NotFoundError):
-                return False
-        return False
+            ok = await handle.take(lease)
+        if ok:
+            self.is_leader = True
+        return ok
 
     async def acquire(self) -> None:
         while not await self.try_acquire():
@@ -103,11 +85,7 @@ class LeaderElector:
         if not self.is_leader:
             return
         try:
-            lease = await self.client.get(LEASE_API_VERSION, "Lease", self.namespace, self.name)
-            spec = lease.get("spec") or {}
-            if spec.get("holderIdentity") == self.identity:
-                spec["holderIdentity"] = ""
-                await self.client.update(lease)
+            await self._lease().release(KEEP)
         except Exception:
             pass
         self.is_leader = False

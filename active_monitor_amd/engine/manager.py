@@ -21,12 +21,15 @@ from __future__ import annotations
 import asyncio
 import logging
 import time
+from collections import deque
 from typing import List, Optional, Tuple
 
 from .. import API_VERSION
 from ..kube.client import EventRecorder, KubeClient
+from ..kube.errors import NotFoundError
 from .leader import LeaderElector
-from .reconciler import HC_KIND, HealthCheckReconciler
+from .reconciler import CACHE_MISS, HC_KIND, HealthCheckReconciler
+from .shards import shard_of
 from .workqueue import WorkQueue
 
 log = logging.getLogger("active_monitor_amd.manager")
@@ -68,6 +71,7 @@ class Manager:
         self.metrics_security = metrics_security
         self.leader_elect = leader_elect
         self.leader_identity = leader_identity
+        self.elector: Optional[LeaderElector] = None
         self._tasks: List[asyncio.Task] = []
         self._sub = None
         self._started = asyncio.Event()
@@ -79,8 +83,6 @@ class Manager:
         self.fatal = asyncio.Event()
         self.fatal_reason: Optional[str] = None
         self.record_latencies = record_latencies
-        from collections import deque
-
         # bounded: an unbounded list leaks ~8B/reconcile on week-long fleets
         self.latencies: "deque" = deque(maxlen=200_000)
         # horizontal scale-out: shard the CR keyspace by stable name hash so
@@ -120,18 +122,17 @@ class Manager:
     async def start(self) -> None:
         """Start informer + workers (+ endpoints); returns once running."""
         if self.leader_elect:
-            elector = LeaderElector(
+            self.elector = LeaderElector(
                 self.client,
                 # LeaderElectionID from the reference (cmd/main.go:88)
                 name="689451f8.keikoproj.io",
                 namespace=self.namespace or "default",
                 identity=self.leader_identity or f"manager-{id(self):x}",
             )
-            await elector.acquire()
-            renew = asyncio.ensure_future(elector.renew_loop())
+            await self.elector.acquire()
+            renew = asyncio.ensure_future(self.elector.renew_loop())
             renew.add_done_callback(self._renew_done)
             self._tasks.append(renew)
-            self.elector = elector
 
         if self.shard_ha:
             from .shards import ShardCoordinator
@@ -185,7 +186,7 @@ class Manager:
         self._stopped = True
         if self._sub is not None:
             self._sub.close()
-        if getattr(self, "wf_hub", None) is not None:
+        if self.wf_hub is not None:
             await self.wf_hub.stop()
         stop_rec = getattr(self.recorder, "stop", None)
         if stop_rec is not None:
@@ -209,8 +210,6 @@ class Manager:
         """An orphaned shard is ours now: surface its CRs (cache + queue) so
         normal reconciles re-arm their timers and resume their schedules —
         the restart-resume path, applied to a subset of the keyspace."""
-        from .shards import shard_of
-
         try:
             objs = await self.client.list(API_VERSION, HC_KIND, self.namespace)
         except Exception as e:
@@ -218,28 +217,19 @@ class Manager:
             return
         n = 0
         for obj in objs:
-            meta = obj.get("metadata") or {}
-            name = meta.get("name", "")
-            if shard_of(name, self.shard_count) != shard:
-                continue
-            key = (meta.get("namespace", ""), name)
-            self.hc_cache[key] = obj
-            await self.queue.add(key)
-            n += 1
+            if await self._ingest(obj, only_shard=shard) is not None:
+                n += 1
         log.warning("adopted shard %d: %d healthchecks enqueued", shard, n)
 
     async def _drop_shard(self, shard: int) -> None:
         """The rightful owner reclaimed the shard: stop its timers/watches and
         forget its CRs so exactly one process drives each key."""
-        from .shards import shard_of
-
         dropped = 0
         for (ns, name) in list(self.hc_cache):
             if shard_of(name, self.shard_count) != shard:
                 continue
             self.hc_cache.pop((ns, name), None)
-            self.reconciler._stop_timer(name, ns)
-            self.reconciler._cancel_watches((ns, name))
+            self.reconciler.forget(ns, name)
             dropped += 1
         log.info("dropped shard %d: released %d healthchecks", shard, dropped)
 
@@ -268,8 +258,6 @@ class Manager:
     def _owns(self, name: str) -> bool:
         if self.shard_count <= 1:
             return True
-        from .shards import shard_of
-
         shard = shard_of(name, self.shard_count)
         if self.coordinator is not None:
             return shard in self.coordinator.owned
@@ -277,35 +265,43 @@ class Manager:
 
     def _cache_lookup(self, namespace: str, name: str):
         """Reconciler-facing cache read; see HealthCheckReconciler.hc_lookup."""
-        from .reconciler import CACHE_MISS
-
         if not self._cache_synced:
             return CACHE_MISS
         return self.hc_cache.get((namespace, name))
+
+    async def _ingest(self, obj: dict, deleted: bool = False,
+                      only_shard: Optional[int] = None):
+        """The one way a HealthCheck enters (or, ``deleted``, leaves) the
+        cache and the queue — from the initial list, a watch event, a shard
+        adoption or a resync. Keys this process does not own are ignored;
+        ``only_shard`` narrows that to one shard (adoption must not re-queue
+        what is already held). The cache changes BEFORE the key is queued.
+        Returns the key, or None when the object was not taken."""
+        meta = obj.get("metadata") or {}
+        name = meta.get("name", "")
+        if only_shard is None:
+            if not self._owns(name):
+                return None
+        elif shard_of(name, self.shard_count) != only_shard:
+            return None
+        key = (meta.get("namespace", ""), name)
+        if deleted:
+            self.hc_cache.pop(key, None)
+        else:
+            self.hc_cache[key] = obj
+        await self.queue.add(key)
+        return key
 
     async def _informer(self) -> None:
         self._sub = self.client.watch(API_VERSION, HC_KIND, self.namespace)
         # initial list AFTER subscribing so no event can slip between the two
         for obj in await self.client.list(API_VERSION, HC_KIND, self.namespace):
-            meta = obj.get("metadata") or {}
-            name = meta.get("name", "")
-            if self._owns(name):
-                self.hc_cache[(meta.get("namespace", ""), name)] = obj
-                await self.queue.add((meta.get("namespace", ""), name))
+            await self._ingest(obj)
         if self.enable_hc_cache:
             self._cache_synced = True
             self.reconciler.hc_lookup = self._cache_lookup
         async for ev in self._sub:
-            obj = ev["object"]
-            meta = obj.get("metadata") or {}
-            name = meta.get("name", "")
-            if self._owns(name):
-                key = (meta.get("namespace", ""), name)
-                if ev["type"] == "DELETED":
-                    self.hc_cache.pop(key, None)
-                else:
-                    self.hc_cache[key] = obj
-                await self.queue.add(key)
+            await self._ingest(ev["object"], deleted=ev["type"] == "DELETED")
 
     async def _resync_loop(self) -> None:
         """Periodic full re-list + re-enqueue of owned keys (the informer
@@ -320,23 +316,13 @@ class Manager:
             except Exception as e:
                 log.warning("resync list failed: %s", e)
                 continue
-            live = set()
-            for obj in objs:
-                meta = obj.get("metadata") or {}
-                name = meta.get("name", "")
-                if not self._owns(name):
-                    continue
-                key = (meta.get("namespace", ""), name)
-                live.add(key)
-                self.hc_cache[key] = obj
-                await self.queue.add(key)
+            # the keys taken (and None, for what is not ours: never a cache key)
+            live = {await self._ingest(obj) for obj in objs}
             # heal cache entries whose DELETED event was lost. A key absent
             # from the list snapshot may simply have been created AFTER the
             # list (its watch event already consumed) — evicting it then
             # would orphan a live CR forever, so suspects are verified with
             # a direct read before reaping.
-            from ..kube.errors import NotFoundError
-
             for key in [k for k in self.hc_cache if k not in live]:
                 try:
                     obj = await self.client.get(

@@ -187,6 +187,13 @@ class HealthCheckReconciler:
         for t in list(self._watch_tasks.get(key, ())):
             t.cancel()
 
+    def forget(self, namespace: str, name: str) -> bool:
+        """Stop driving a key: its repeat timer is stopped and its in-flight
+        watches are cancelled. True when there was a timer to stop."""
+        stopped = self._stop_timer(name, namespace)
+        self._cancel_watches((namespace, name))
+        return stopped
+
     def active_watches(self) -> int:
         return sum(len(v) for v in self._watch_tasks.values())
 
@@ -269,7 +276,7 @@ class HealthCheckReconciler:
             # CR deleted: stop the repeat timer so self-scheduling halts
             # (:180-184); in-flight watches are cancelled proactively (the
             # reference lets them die on workflow NotFound after GC).
-            if self._stop_timer(name, namespace):
+            if self.forget(namespace, name):
                 log.info("cancelled rescheduled workflow for deleted healthcheck %s", name)
                 await self.recorder.event(
                     {"apiVersion": API_VERSION, "kind": HC_KIND,
@@ -277,7 +284,6 @@ class HealthCheckReconciler:
                     "Normal", "Normal",
                     "Cancelling workflow for this healthcheck due to deletion",
                 )
-            self._cancel_watches((namespace, name))
             return ReconcileResult()
         hc = HealthCheck.from_dict(obj)
         return await self._process_or_recover(hc, from_timer=TIMER_FLAG in flags)

@@ -27,17 +27,16 @@ from __future__ import annotations
 
 import asyncio
 import logging
-import time
 import zlib
 from typing import Awaitable, Callable, Optional, Set
 
-from ..api.types import k8s_now, parse_k8s_time
+from ..api.types import k8s_now
 from ..kube.client import KubeClient
-from ..kube.errors import AlreadyExistsError, ApiError, ConflictError, NotFoundError
+from ..kube.errors import ApiError
+from .lease import LEASE_API_VERSION  # noqa: F401 — tests import it from here
+from .lease import DROP, STAMP, Lease
 
 log = logging.getLogger("active_monitor_amd.shards")
-
-LEASE_API_VERSION = "coordination.k8s.io/v1"
 
 
 def shard_of(name: str, shard_count: int) -> int:
@@ -75,91 +74,55 @@ class ShardCoordinator:
     def _lease_name(self, shard: int) -> str:
         return f"active-monitor-shard-{shard}-of-{self.shard_count}"
 
-    def _lease_obj(self, shard: int) -> dict:
-        return {
-            "apiVersion": LEASE_API_VERSION,
-            "kind": "Lease",
-            "metadata": {"name": self._lease_name(shard), "namespace": self.namespace},
-            "spec": {
-                "holderIdentity": self.identity,
-                "leaseDurationSeconds": int(self.lease_duration),
-                "renewTime": k8s_now(),
-            },
-        }
-
-    def _expired(self, spec: dict) -> bool:
-        holder = spec.get("holderIdentity")
-        if not holder:
-            return True
-        renew = parse_k8s_time(spec.get("renewTime"))
+    def _lease(self, shard: int) -> Lease:
         # k8s timestamps have 1s resolution; pad the window so a
         # freshly-renewed lease never reads as expired
-        return renew is None or (time.time() - renew.timestamp()) > (
-            self.lease_duration + 1.0
-        )
+        return Lease(self.client, self.namespace, self._lease_name(shard),
+                     self.identity, self.lease_duration, expiry_pad=1.0)
 
     # -- lease ops ----------------------------------------------------------
 
     async def _try_acquire(self, shard: int) -> bool:
         """Acquire the shard's lease if unheld/expired/ours/preferred-to-us."""
-        try:
-            lease = await self.client.get(
-                LEASE_API_VERSION, "Lease", self.namespace, self._lease_name(shard)
-            )
-        except NotFoundError:
-            try:
-                await self.client.create(self._lease_obj(shard))
-                return True
-            except AlreadyExistsError:
-                return False
+        handle = self._lease(shard)
+        lease = await handle.read()
+        if lease is None:
+            return await handle.create()
         spec = lease.get("spec") or {}
         holder = spec.get("holderIdentity")
-        preferred = spec.get("preferredHolder")
-        if holder != self.identity:
-            if not self._expired(spec):
-                return False
-            if preferred and preferred != self.identity:
-                # a graceful release aimed at the preferred owner: give it a
-                # full lease window before anyone else may adopt (its own
-                # death is then indistinguishable from expiry and the lease
-                # becomes free-for-all)
-                renew = parse_k8s_time(spec.get("renewTime"))
-                if renew is not None and (
-                    time.time() - renew.timestamp()
-                ) <= self.lease_duration + 1.0:
-                    return False
-        fresh = self._lease_obj(shard)["spec"]
-        if preferred and preferred != self.identity:
-            fresh["preferredHolder"] = preferred  # keep a pending reclaim
-        lease["spec"] = fresh
-        try:
-            await self.client.update(lease)
-            return True
-        except (ConflictError, NotFoundError):
+        pending = spec.get("preferredHolder")
+        if pending == self.identity:
+            pending = None  # taking it satisfies our own reclaim
+        # a foreign holder keeps the lease for its window. So does a blank one
+        # left by a graceful release aimed at a preferred owner: that owner
+        # gets a full window before anyone else may adopt (its own death is
+        # then indistinguishable from expiry and the lease is free-for-all)
+        if holder != self.identity and (holder or pending) and not handle.expired(spec):
             return False
+        keep = {"preferredHolder": pending} if pending else {}  # a reclaim stays pending
+        return await handle.take(lease, **keep)
 
     async def _request_reclaim(self, shard: int) -> None:
         """Home process asks a live adopter for its shard back
         (Lease.spec.preferredHolder, the KEP-4355 handshake)."""
+        handle = self._lease(shard)
         try:
-            lease = await self.client.get(
-                LEASE_API_VERSION, "Lease", self.namespace, self._lease_name(shard)
-            )
+            lease = await handle.read()
+            if lease is None:
+                return
             spec = lease.get("spec") or {}
             if spec.get("preferredHolder") != self.identity:
                 spec["preferredHolder"] = self.identity
-                await self.client.update(lease)
+                await handle.write(lease)
         except (ApiError, asyncio.CancelledError):
             pass
 
     async def _renew_owned(self, shard: int) -> bool:
         """Renew an owned shard; honors a pending reclaim by releasing.
         Returns False when the shard was lost/released."""
-        try:
-            lease = await self.client.get(
-                LEASE_API_VERSION, "Lease", self.namespace, self._lease_name(shard)
-            )
-        except NotFoundError:
+        handle = self._lease(shard)
+        lease = await handle.read()
+        if lease is None:
             return await self._try_acquire(shard)
         spec = lease.get("spec") or {}
         if spec.get("holderIdentity") != self.identity:
@@ -168,21 +131,12 @@ class ShardCoordinator:
         if shard != self.home and preferred and preferred != self.identity:
             # the rightful owner wants it back: release gracefully (the
             # renewTime stamp opens the preferred owner's priority window)
-            spec["holderIdentity"] = ""
-            spec["renewTime"] = k8s_now()
-            try:
-                await self.client.update(lease)
-            except (ConflictError, NotFoundError):
-                pass
+            await handle.release(STAMP, lease)
             return False
         spec["renewTime"] = k8s_now()
         if preferred == self.identity:
             spec.pop("preferredHolder", None)  # reclaim satisfied
-        try:
-            await self.client.update(lease)
-            return True
-        except (ConflictError, NotFoundError):
-            return False
+        return await handle.write(lease)
 
     # -- lifecycle ----------------------------------------------------------
 
@@ -206,17 +160,11 @@ class ShardCoordinator:
             except (asyncio.CancelledError, Exception):
                 pass
         # release everything we hold so successors need not wait out the TTL
+        # (renewTime dropped: immediate expiry, no window)
         for shard in list(self.owned):
             try:
-                lease = await self.client.get(
-                    LEASE_API_VERSION, "Lease", self.namespace, self._lease_name(shard)
-                )
-                spec = lease.get("spec") or {}
-                if spec.get("holderIdentity") == self.identity:
-                    spec["holderIdentity"] = ""
-                    spec.pop("renewTime", None)  # immediate expiry: no window
-                    await self.client.update(lease)
-            except (ApiError, Exception):
+                await self._lease(shard).release(DROP)
+            except Exception:
                 pass
         self.owned.clear()
 

@@ -26,7 +26,7 @@ import os
 import signal
 import sys
 
-from .memory import MemoryApiServer, healthcheck_schemas
+from .memory import healthcheck_schemas
 from .server import ApiServerFrontend
 
 
@@ -101,73 +101,88 @@ def read_accepted_tokens(path: str) -> set:
     return tokens
 
 
-def open_durable_store(data_dir: str, schemas=None):
+def _to_stderr(message: str) -> None:
+    print(message, file=sys.stderr, flush=True)
+
+
+def open_durable_store(data_dir: str, schemas=None, info=_to_stderr, error=_to_stderr):
     """Open the store kept in ``data_dir`` and say what was found; on a
-    locked or unreadable directory print the reason and return None — the
+    locked or unreadable directory say the reason and return None — the
     caller exits 1 and never starts an empty store over it."""
+    from . import MemoryApiServer  # looked up late, see open_store
     from .persist import StoreError
 
     try:
         server = MemoryApiServer.open(data_dir, schemas=schemas)
     except (StoreError, OSError) as e:
-        print(f"cannot open data directory: {e}", file=sys.stderr, flush=True)
+        error(f"cannot open data directory: {e}")
         return None
-    print(f"data directory {server.data_dir}: loaded {len(server)} objects, "
-          f"resourceVersion {server.resource_version()}",
-          file=sys.stderr, flush=True)
+    info(f"data directory {server.data_dir}: loaded {len(server)} objects, "
+         f"resourceVersion {server.resource_version()}")
     return server
+
+
+def open_store(data_dir, schema_validation: bool = True,
+               info=_to_stderr, error=_to_stderr):
+    """The store of a standalone process, for both entry points (this module
+    and ``cmd.main --backend memory``): says which schemas validate, then
+    opens ``data_dir`` — or, without one, starts an empty store. Returns None
+    when the directory cannot be used. ``info``/``error`` take one message."""
+    # the class is looked up on the package when called, not bound at import:
+    # tests substitute a recording subclass there
+    from . import MemoryApiServer
+
+    schemas, schema_line = standalone_schemas(schema_validation)
+    info(schema_line)
+    if data_dir:
+        return open_durable_store(data_dir, schemas, info, error)
+    return MemoryApiServer(schemas=schemas)
+
+
+def build_engine(kind: str, client, data_dir, **options):
+    """The workflow engine that runs inside a standalone process, or None for
+    ``"none"``. Over a data directory it recovers what the last process left
+    (a workflow found Running is failed as interrupted, never run again)."""
+    from ..workflow import LocalWorkflowEngine, ScriptedWorkflowEngine
+
+    if kind == "none":
+        return None
+    cls = {"local": LocalWorkflowEngine, "scripted-bench": ScriptedWorkflowEngine}[kind]
+    return cls(client, recover=bool(data_dir), **options)
+
+
+def stop_on_signals(stop: asyncio.Event) -> asyncio.Event:
+    """Have SIGINT and SIGTERM set ``stop`` on the running loop."""
+    loop = asyncio.get_running_loop()
+    for sig in (signal.SIGINT, signal.SIGTERM):
+        try:
+            loop.add_signal_handler(sig, stop.set)
+        except (NotImplementedError, RuntimeError):  # pragma: no cover - non-unix
+            pass
+    return stop
 
 
 async def amain(args) -> int:
     from .client import MemoryClient
 
-    schemas, schema_line = standalone_schemas(
-        getattr(args, "schema_validation", True))
-    print(schema_line, file=sys.stderr, flush=True)
-    data_dir = getattr(args, "data_dir", None)
-    if data_dir:
-        server = open_durable_store(data_dir, schemas)
-        if server is None:
-            return 1
-    else:
-        server = MemoryApiServer(schemas=schemas)
-    accepted = None
-    if getattr(args, "token_file", None):
-        accepted = read_accepted_tokens(args.token_file)
+    server = open_store(args.data_dir, args.schema_validation)
+    if server is None:
+        return 1
+    accepted = read_accepted_tokens(args.token_file) if args.token_file else None
     frontend = ApiServerFrontend(server, args.host, args.port,
                                  accepted_tokens=accepted)
     await frontend.start()
 
-    engine = None
+    options = {"ttl_seconds": args.engine_ttl}
     if args.engine == "scripted-bench":
-        from ..workflow import ScriptedWorkflowEngine
-
-        engine = ScriptedWorkflowEngine(
-            MemoryClient(server),
-            policy=bench_policy(args.remedy_frac),
-            delay=args.engine_delay,
-            ttl_seconds=args.engine_ttl,
-            recover=bool(data_dir),
-        )
-    elif args.engine == "local":
-        from ..workflow import LocalWorkflowEngine
-
-        engine = LocalWorkflowEngine(MemoryClient(server), ttl_seconds=args.engine_ttl,
-                                     recover=bool(data_dir))
+        options.update(policy=bench_policy(args.remedy_frac), delay=args.engine_delay)
+    engine = build_engine(args.engine, MemoryClient(server), args.data_dir, **options)
     if engine is not None:
         await engine.start()
 
     print("READY " + json.dumps({"url": frontend.url, "port": frontend.port}),
           flush=True)
-
-    stop = asyncio.Event()
-    loop = asyncio.get_running_loop()
-    for sig in (signal.SIGINT, signal.SIGTERM):
-        try:
-            loop.add_signal_handler(sig, stop.set)
-        except (NotImplementedError, RuntimeError):  # pragma: no cover
-            pass
-    await stop.wait()
+    await stop_on_signals(asyncio.Event()).wait()
 
     if engine is not None:
         await engine.stop()
