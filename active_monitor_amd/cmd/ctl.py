@@ -9,6 +9,10 @@ framework's standalone ``--serve-api`` endpoint:
     amctl --server ... describe hc inline-hello -n health
     amctl --server ... apply -f examples/inline-hello.yaml
     amctl --server ... delete hc inline-hello -n health
+    amctl --server ... logs hc inline-hello -n health
+
+``logs`` needs the standalone apiserver: on a cluster the output of a
+workflow is the logs of its pods (``kubectl logs``, ``argo logs``).
 """
 from __future__ import annotations
 
@@ -166,6 +170,76 @@ async def cmd_delete(client: HttpClient, args) -> int:
     return 0
 
 
+class _LogsError(Exception):
+    """``amctl logs`` cannot show anything; the message says why."""
+
+
+async def _hc_workflow(client: HttpClient, args) -> Dict[str, Any]:
+    """The Workflow whose log ``logs hc NAME`` shows: the last failed run
+    of a check that stands Failed, else the last successful one."""
+    hc = await client.get(API_VERSION, "HealthCheck", args.namespace, args.name)
+    status = hc.get("status") or {}
+    if args.failed:
+        which = "lastFailedWorkflow"
+    elif args.succeeded:
+        which = "lastSuccessfulWorkflow"
+    else:
+        which = ("lastFailedWorkflow" if status.get("status") == "Failed"
+                 else "lastSuccessfulWorkflow")
+    wf_name = status.get(which)
+    if not wf_name:
+        if not status.get("lastFailedWorkflow") and not status.get("lastSuccessfulWorkflow"):
+            raise _LogsError(f"healthcheck {args.name} has not run yet")
+        kind = "failed" if which == "lastFailedWorkflow" else "successful"
+        raise _LogsError(f"healthcheck {args.name} has no {kind} workflow yet")
+    # the check and the remedy name a namespace each; the HealthCheck's own
+    # is where a workflow without one goes
+    spec = hc.get("spec") or {}
+    namespaces: List[str] = []
+    for key in ("workflow", "remedyworkflow"):
+        ns = ((spec.get(key) or {}).get("resource") or {}).get("namespace")
+        if ns and ns not in namespaces:
+            namespaces.append(ns)
+    if args.namespace not in namespaces:
+        namespaces.append(args.namespace)
+    for ns in namespaces:
+        try:
+            return await client.get(WF_API_VERSION, "Workflow", ns, wf_name)
+        except NotFoundError:
+            continue
+    raise _LogsError(
+        f"workflow {wf_name} of healthcheck {args.name} is gone: a workflow "
+        "and its logs are deleted together once the engine TTL has passed")
+
+
+async def cmd_logs(client: HttpClient, args) -> int:
+    try:
+        if ALIASES[args.resource][1] == "HealthCheck":
+            wf = await _hc_workflow(client, args)
+        else:
+            wf = await client.get(WF_API_VERSION, "Workflow", args.namespace, args.name)
+        meta = wf["metadata"]
+        phase = (wf.get("status") or {}).get("phase", "") or "Pending"
+        print(f'==> workflow {meta["name"]} ({phase}) <==', file=sys.stderr, flush=True)
+        out = sys.stdout.buffer
+        try:
+            async for chunk in client.logs(
+                meta.get("namespace", ""), meta["name"], node=args.node,
+                follow=args.follow, tail_lines=args.tail,
+                prefix=not (args.no_prefix or args.node is not None),
+            ):
+                out.write(chunk)
+                out.flush()
+        except NotFoundError as e:
+            raise _LogsError(
+                f'{e.message} (workflow {meta["name"]}: a workflow and its logs '
+                "are deleted together once the engine TTL has passed)")
+    except _LogsError as e:
+        print(f"Error: {e}", file=sys.stderr)
+        return 1
+    return 0
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="amctl", description=__doc__.splitlines()[0])
     p.add_argument("--server", required=True, help="apiserver URL")
@@ -199,6 +273,26 @@ def build_parser() -> argparse.ArgumentParser:
     rm.add_argument("resource", choices=sorted(ALIASES))
     rm.add_argument("name")
     rm.add_argument("-n", "--namespace", default="health")
+
+    lg = sub.add_parser(
+        "logs", help="what a workflow's leaves printed (standalone apiserver)")
+    lg.add_argument("resource", choices=sorted(
+        a for a, (_, kind) in ALIASES.items() if kind in ("HealthCheck", "Workflow")))
+    lg.add_argument("name")
+    lg.add_argument("-n", "--namespace", default="health")
+    lg.add_argument("--node", default=None,
+                    help="one node, by id or display name (default: all)")
+    lg.add_argument("-f", "--follow", action="store_true",
+                    help="keep printing until the workflow finishes")
+    lg.add_argument("--tail", type=int, default=None, metavar="N",
+                    help="only the last N lines of each node")
+    which = lg.add_mutually_exclusive_group()
+    which.add_argument("--failed", action="store_true",
+                       help="hc: the last failed workflow, whatever the status")
+    which.add_argument("--succeeded", action="store_true",
+                       help="hc: the last successful workflow")
+    lg.add_argument("--no-prefix", action="store_true",
+                    help="do not put the node's display name before each line")
     return p
 
 
@@ -211,7 +305,8 @@ async def run(args) -> int:
     await client.start()
     try:
         handler = {"get": cmd_get, "describe": cmd_describe,
-                   "apply": cmd_apply, "delete": cmd_delete}[args.command]
+                   "apply": cmd_apply, "delete": cmd_delete,
+                   "logs": cmd_logs}[args.command]
         return await handler(client, args)
     except NotFoundError as e:
         print(f"Error: {e}", file=sys.stderr)

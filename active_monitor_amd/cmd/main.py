@@ -32,6 +32,8 @@ def parse_bind_address(addr: str) -> Optional[Tuple[str, int]]:
 
 
 def build_parser() -> argparse.ArgumentParser:
+    from ..kube.standalone import add_log_flags
+
     p = argparse.ArgumentParser(
         prog="active-monitor-amd",
         description="HealthCheck/Remedy controller (clean-room active-monitor)",
@@ -86,6 +88,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="memory backend: store HealthChecks as given instead "
                         "of validating and pruning them by the CRD schema "
                         "(also: AM_SCHEMA_VALIDATION=0 in the environment)")
+    add_log_flags(p)
     p.add_argument("--shard-index", type=int, default=0,
                    help="this controller's shard (keyspace split by CR-name hash)")
     p.add_argument("--shard-count", type=int, default=1,
@@ -120,7 +123,7 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         gc.set_threshold(args.gc_threshold, 50, 50)
     # looked up when called, not at import: tests substitute the Manager
     from ..engine import Manager
-    from ..kube.standalone import build_engine, open_store, stop_on_signals
+    from ..kube.standalone import build_engine, open_logs, open_store, stop_on_signals
 
     level = {"debug": logging.DEBUG, "info": logging.INFO,
              "warn": logging.WARNING, "error": logging.ERROR}.get(
@@ -138,7 +141,7 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         )
     log = logging.getLogger("active_monitor_amd.main")
 
-    store = engine = frontend = None  # the memory backend's three parts
+    store = engine = frontend = logs = None  # the memory backend's parts
     if args.backend == "http":
         from ..kube.config import get_config
 
@@ -162,13 +165,14 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         if store is None:
             return 1
         client = MemoryClient(store)
+        logs = open_logs(args, args.workflow_engine, store, log.info)
         engine = build_engine(args.workflow_engine, client, args.data_dir,
-                              namespace=args.namespace)
+                              logs=logs, namespace=args.namespace)
         if args.serve_api:
             from ..kube.server import ApiServerFrontend
 
             addr = parse_bind_address(args.serve_api)
-            frontend = ApiServerFrontend(store, addr[0], addr[1])
+            frontend = ApiServerFrontend(store, addr[0], addr[1], logs=logs)
             await frontend.start()
             log.info("serving Kubernetes REST API at %s", frontend.url)
 
@@ -227,6 +231,8 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         await engine.stop()
     if frontend is not None:
         await frontend.stop()
+    if logs is not None:
+        logs.close()
     if store is not None:
         store.close()
     else:
@@ -235,12 +241,20 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
 
 
 def main(argv=None) -> int:
+    from ..kube.standalone import check_log_flags
+
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.data_dir and args.backend != "memory":
         parser.error("--data-dir applies to --backend memory only")
     if not args.schema_validation and args.backend != "memory":
         parser.error("--no-schema-validation applies to --backend memory only")
+    for flag, given in (("--log-max-bytes", args.log_max_bytes is not None),
+                        ("--log-max-total-bytes", args.log_max_total_bytes is not None),
+                        ("--no-workflow-logs", not args.workflow_logs)):
+        if given and args.backend != "memory":
+            parser.error(f"{flag} applies to --backend memory only")
+    check_log_flags(parser, args)
     try:
         return asyncio.run(run(args))
     except KeyboardInterrupt:

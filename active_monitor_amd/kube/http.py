@@ -31,7 +31,7 @@ from .errors import (
     NotFoundError,
     UnauthorizedError,
 )
-from .registry import DEFAULT_REGISTRY, Registry
+from .registry import DEFAULT_REGISTRY, WF_API_VERSION, WF_KIND, Registry
 
 log = logging.getLogger("active_monitor_amd.kube.http")
 
@@ -643,6 +643,49 @@ class HttpClient:
 
     async def delete(self, api_version: str, kind: str, namespace: str, name: str) -> None:
         await self._request("DELETE", self._object_path(api_version, kind, namespace, name))
+
+    async def logs(self, namespace: str, name: str, node: Optional[str] = None,
+                   follow: bool = False, tail_lines: Optional[int] = None,
+                   limit_bytes: Optional[int] = None,
+                   prefix: bool = False) -> AsyncIterator[bytes]:
+        """The ``log`` subresource of a Workflow (a standalone apiserver's
+        stand-in for the logs of the workflow's pods), as it arrives. With
+        ``follow`` it ends when the server ends it: the run has finished.
+        Credentials as for every request, with one refresh-and-retry on 401;
+        a stream that breaks is not resumed."""
+        if self._session is None:
+            raise RuntimeError("HttpClient.start() must be called before requests")
+        params: Dict[str, str] = {}
+        if node is not None:
+            params["node"] = node
+        if follow:
+            params["follow"] = "true"
+        if tail_lines is not None:
+            params["tailLines"] = str(tail_lines)
+        if limit_bytes is not None:
+            params["limitBytes"] = str(limit_bytes)
+        if prefix:
+            params["prefix"] = "true"
+        url = self.base_url + self._object_path(
+            WF_API_VERSION, WF_KIND, namespace, name) + "/log"
+        source = self._credentials
+        for attempt in (0, 1):
+            await self._limiter.acquire()
+            self.request_count += 1
+            cred = await source.get() if source is not None else None
+            async with self._session.get(
+                url, params=params, headers=self._session_auth(cred),
+                timeout=aiohttp.ClientTimeout(total=None),
+            ) as resp:
+                if resp.status == 401 and source is not None and attempt == 0:
+                    await resp.read()
+                    source.invalidate(cred)
+                    continue
+                if resp.status >= 400:
+                    raise _error_for(resp.status, await resp.read())
+                async for chunk in resp.content.iter_any():
+                    yield chunk
+                return
 
     def watch(self, api_version: str, kind: str, namespace: Optional[str] = None) -> HttpSubscription:
         return HttpSubscription(self, api_version, kind, namespace)

@@ -23,7 +23,14 @@ from typing import List, Optional, Set, Tuple
 
 from ..utils import wirecodec
 from ..utils.wirecodec import EXPECT_CONTINUE, WANT_TABLE
-from .errors import ApiError, ExpiredError, InvalidError, UnauthorizedError
+from .errors import (
+    ApiError,
+    BadRequestError,
+    ExpiredError,
+    InvalidError,
+    NotFoundError,
+    UnauthorizedError,
+)
 from .memory import (
     MemoryApiServer,
     fields_match,
@@ -32,6 +39,7 @@ from .memory import (
     parse_field_selector,
     parse_label_selector,
 )
+from .registry import WF_API_VERSION, WF_KIND
 
 log = logging.getLogger("active_monitor_amd.kube.server")
 
@@ -111,6 +119,11 @@ def _route(path: str) -> Optional[Tuple[str, str, str, str, str]]:
     return api_version, namespace, plural, name, subresource
 
 
+class _MethodNotAllowed(ApiError):
+    code = 405
+    reason = "MethodNotAllowed"
+
+
 class _Warned:
     """A response object that goes out with ``Warning`` headers: what a write
     returns when fields were pruned under ``fieldValidation=Warn``. Every
@@ -155,8 +168,11 @@ _OPEN_PATHS = frozenset({
 
 class ApiServerFrontend:
     def __init__(self, server: MemoryApiServer, host: str = "127.0.0.1", port: int = 0,
-                 accepted_tokens: Optional[Set[str]] = None):
+                 accepted_tokens: Optional[Set[str]] = None, logs=None):
         self.server = server
+        #: the workflow.logs.LogStore behind the Workflows' ``log``
+        #: subresource, or None: every such request is then a 404
+        self.logs = logs
         self.host = host
         self.port = port
         #: None = open to everyone. A set = bearer-token authn: every request
@@ -188,9 +204,10 @@ class ApiServerFrontend:
                 pass
 
     def kick_watches(self) -> None:
-        """Terminate every open watch stream (server stays up). Clients see a
-        clean end-of-stream and reconnect with their resourceVersion — the
-        fault-injection hook for RV-expiry/resume conformance tests."""
+        """Terminate every open watch stream and every followed log (server
+        stays up). Clients see a clean end-of-stream and reconnect with their
+        resourceVersion — the fault-injection hook for RV-expiry/resume
+        conformance tests."""
         for sub in list(self._live_subs):
             sub.close()
 
@@ -245,6 +262,10 @@ class ApiServerFrontend:
                 if query.get("watch") in ("true", "1"):
                     await self._serve_watch(writer, path, query)
                     return  # watch streams own the connection
+                if path.endswith("/log") and self._is_log_route(path):
+                    if await self._serve_log(writer, method, path, query):
+                        return  # so does a followed log
+                    continue
                 status, obj = self._serve_unary(method, path, query, body,
                                                 content_type)
                 if (flags & WANT_TABLE and method == "GET" and status == 200
@@ -329,6 +350,14 @@ class ApiServerFrontend:
                 "kind": kind,
                 "verbs": ["create", "delete", "get", "list", "patch", "update", "watch"],
             })
+            if (av, kind) == (WF_API_VERSION, WF_KIND):
+                resources.append({
+                    "name": f"{info.plural}/log",
+                    "singularName": "",
+                    "namespaced": True,
+                    "kind": kind,
+                    "verbs": ["get"],
+                })
             if (av, kind) == ("activemonitor.keikoproj.io/v1alpha1", "HealthCheck"):
                 resources[-1]["shortNames"] = ["hc", "hcs"]
                 resources.append({
@@ -511,6 +540,86 @@ class ApiServerFrontend:
             "columnDefinitions": defs,
             "rows": rows,
         }
+
+    # -- workflow logs ------------------------------------------------------
+
+    def _is_log_route(self, path: str) -> bool:
+        route = _route(path)
+        if route is None or route[4] != "log" or route[0] != WF_API_VERSION:
+            return False
+        try:
+            return self.server.registry.by_plural(route[0], route[2]).kind == WF_KIND
+        except KeyError:
+            return False
+
+    async def _serve_log(self, writer: asyncio.StreamWriter, method: str,
+                         path: str, query: dict) -> bool:
+        """``GET .../workflows/{name}/log``: what the workflow's leaves
+        printed, as text/plain. With ``follow=true`` the response is chunked
+        and ends when the run does (or with kick_watches/stop); True is then
+        returned and the connection is not used again."""
+        _, namespace, _, name, _ = _route(path)
+        try:
+            if method != "GET":
+                raise _MethodNotAllowed(f"unsupported method {method}")
+            numbers = {}
+            for key in ("tailLines", "limitBytes"):
+                if query.get(key) is not None:
+                    try:
+                        numbers[key] = int(query[key])
+                    except ValueError:
+                        raise BadRequestError(
+                            f"{key} must be an integer, not {query[key]!r}")
+            # NotFound: the Workflow does not exist
+            self.server.get(WF_API_VERSION, WF_KIND, namespace, name)
+            if self.logs is None:
+                raise NotFoundError(
+                    f"workflow {namespace}/{name} has no logs: this server "
+                    "keeps no workflow logs")
+            if not self.logs.has_run(namespace, name):
+                raise NotFoundError(
+                    f"workflow {namespace}/{name} has no logs: it was not run "
+                    "by the local executor, or its logs were dropped for the "
+                    "total size cap")
+            follow = query.get("follow") in ("true", "1")
+            stream = self.logs.read(
+                namespace, name, node=query.get("node") or None, follow=follow,
+                tail_lines=numbers.get("tailLines"),
+                limit_bytes=numbers.get("limitBytes"),
+                prefix=query.get("prefix") in ("true", "1"),
+            )  # NotFound: the node is unknown
+        except ApiError as e:
+            status, body = _failure(e)
+            writer.write(wirecodec.frame(_json_prefix(status), body))
+            await writer.drain()
+            return False
+        if not follow:
+            payload = b"".join([chunk async for chunk in stream])
+            writer.write(
+                b"HTTP/1.1 200 OK\r\nContent-Type: text/plain\r\n"
+                b"Content-Length: %d\r\n\r\n" % len(payload) + payload
+            )
+            await writer.drain()
+            return False
+        self._live_subs.append(stream)
+        try:
+            writer.write(
+                b"HTTP/1.1 200 OK\r\nContent-Type: text/plain\r\n"
+                b"Transfer-Encoding: chunked\r\nConnection: close\r\n\r\n"
+            )
+            await writer.drain()
+            async for chunk in stream:
+                writer.write(b"%x\r\n%s\r\n" % (len(chunk), chunk))
+                await writer.drain()
+            writer.write(b"0\r\n\r\n")
+            await writer.drain()
+        except (ConnectionError, asyncio.CancelledError):
+            pass
+        finally:
+            await stream.aclose()
+            if stream in self._live_subs:
+                self._live_subs.remove(stream)
+        return True
 
     # -- watch --------------------------------------------------------------
 

@@ -30,6 +30,11 @@ from .memory import healthcheck_schemas
 from .server import ApiServerFrontend
 
 
+#: where the workflow logs live in a data directory; the journal
+#: (kube/persist.py) knows its own files only and leaves it alone
+LOGS_SUBDIR = "logs"
+
+
 def bench_policy(remedy_frac: float):
     """The bench fleet's workflow outcomes, decodable from workflow names
     (bench.py make_cr): CR ``hc-NNNNN`` fails its checks iff NNNNN%100 <
@@ -80,7 +85,62 @@ def parse_args(argv=None):
                    help="store HealthChecks as given instead of validating "
                         "and pruning them by the CRD schema (also: "
                         "AM_SCHEMA_VALIDATION=0 in the environment)")
-    return p.parse_args(argv)
+    add_log_flags(p)
+    args = p.parse_args(argv)
+    check_log_flags(p, args)
+    return args
+
+
+def add_log_flags(p: argparse.ArgumentParser) -> None:
+    """The flags of the workflow log store, for both entry points."""
+    p.add_argument("--log-max-bytes", type=int, default=None, metavar="N",
+                   help="local engine: keep at most N bytes of output per "
+                        "workflow node, the newest (default: 1 MiB)")
+    p.add_argument("--log-max-total-bytes", type=int, default=None, metavar="N",
+                   help="local engine: keep at most N bytes of workflow "
+                        "output in all; beyond it whole finished runs are "
+                        "dropped, oldest first (default: 256 MiB)")
+    p.add_argument("--no-workflow-logs", dest="workflow_logs",
+                   action="store_false",
+                   help="local engine: keep no workflow output")
+
+
+def check_log_flags(p: argparse.ArgumentParser, args) -> None:
+    for flag, value in (("--log-max-bytes", args.log_max_bytes),
+                        ("--log-max-total-bytes", args.log_max_total_bytes)):
+        if value is not None and value < 2:
+            p.error(f"{flag} must be 2 or more")
+
+
+def open_logs(args, engine_kind: str, server, info=None):
+    """The workflow log store of a standalone process: ``<data-dir>/logs``,
+    or a temporary directory without ``--data-dir``. None, and ``workflow
+    logs: off``, unless the local engine runs here and logs are wanted. What
+    an earlier process left is served again, less the runs whose Workflow is
+    no longer in ``server``."""
+    from ..workflow import logs
+    from .registry import WF_API_VERSION, WF_KIND
+
+    info = info or _to_stderr
+    if engine_kind != "local" or not args.workflow_logs:
+        info("workflow logs: off")
+        return None
+    caps = {}
+    if args.log_max_bytes is not None:
+        caps["max_node_bytes"] = args.log_max_bytes
+    if args.log_max_total_bytes is not None:
+        caps["max_total_bytes"] = args.log_max_total_bytes
+    if args.data_dir:
+        live = [
+            ((wf["metadata"].get("namespace", "")), wf["metadata"]["name"])
+            for wf in server.list(WF_API_VERSION, WF_KIND)
+        ]
+        store = logs.LogStore.open(
+            os.path.join(args.data_dir, LOGS_SUBDIR), live=live, **caps)
+    else:
+        store = logs.LogStore(**caps)
+    info(f"workflow logs: {store.describe()}")
+    return store
 
 
 def standalone_schemas(enabled: bool = True):
@@ -139,14 +199,17 @@ def open_store(data_dir, schema_validation: bool = True,
     return MemoryApiServer(schemas=schemas)
 
 
-def build_engine(kind: str, client, data_dir, **options):
+def build_engine(kind: str, client, data_dir, logs=None, **options):
     """The workflow engine that runs inside a standalone process, or None for
     ``"none"``. Over a data directory it recovers what the last process left
-    (a workflow found Running is failed as interrupted, never run again)."""
+    (a workflow found Running is failed as interrupted, never run again).
+    ``logs`` is the local engine's log store."""
     from ..workflow import LocalWorkflowEngine, ScriptedWorkflowEngine
 
     if kind == "none":
         return None
+    if kind == "local":
+        options["logs"] = logs
     cls = {"local": LocalWorkflowEngine, "scripted-bench": ScriptedWorkflowEngine}[kind]
     return cls(client, recover=bool(data_dir), **options)
 
@@ -169,14 +232,16 @@ async def amain(args) -> int:
     if server is None:
         return 1
     accepted = read_accepted_tokens(args.token_file) if args.token_file else None
+    logs = open_logs(args, args.engine, server)
     frontend = ApiServerFrontend(server, args.host, args.port,
-                                 accepted_tokens=accepted)
+                                 accepted_tokens=accepted, logs=logs)
     await frontend.start()
 
     options = {"ttl_seconds": args.engine_ttl}
     if args.engine == "scripted-bench":
         options.update(policy=bench_policy(args.remedy_frac), delay=args.engine_delay)
-    engine = build_engine(args.engine, MemoryClient(server), args.data_dir, **options)
+    engine = build_engine(args.engine, MemoryClient(server), args.data_dir,
+                          logs=logs, **options)
     if engine is not None:
         await engine.start()
 
@@ -187,6 +252,8 @@ async def amain(args) -> int:
     if engine is not None:
         await engine.stop()
     await frontend.stop()
+    if logs is not None:
+        logs.close()
     server.close()
     return 0
 

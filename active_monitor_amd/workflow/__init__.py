@@ -6,10 +6,12 @@ from .engines import (
     always_succeed,
     never_complete,
 )
+from .logs import LogStore
 from .validate import validate_workflow_spec
 
 __all__ = [
     "LocalWorkflowEngine",
+    "LogStore",
     "ScriptedWorkflowEngine",
     "always_fail",
     "always_succeed",

@@ -8,11 +8,12 @@
     and remedy workflows are linted. Prints one line per problem; exit status
     1 when there are any.
 
-``run FILE [-p name=value ...] [--remedy]``
+``run FILE [-p name=value ...] [--remedy] [--logs]``
     Execute one workflow with the local executor against a throw-away
     in-memory store and print the phase and a node table. For a HealthCheck
-    the check workflow runs (``--remedy``: the remedy workflow). Exit status
-    0 for ``Succeeded``, 1 for ``Failed``.
+    the check workflow runs (``--remedy``: the remedy workflow). ``--logs``
+    adds what every leaf printed, stdout and stderr, under a ``--- NODE ---``
+    line each. Exit status 0 for ``Succeeded``, 1 for ``Failed``.
 
 Neither needs a server.
 """
@@ -32,8 +33,10 @@ from ..engine.parse import (
     parse_workflow_from_healthcheck,
 )
 from ..kube import MemoryApiServer, MemoryClient
+from ..kube.errors import NotFoundError
 from ..kube.registry import WF_API_VERSION, WF_KIND
 from . import LocalWorkflowEngine, validate_workflow_spec
+from .logs import LogStore
 
 
 def _inline(wf: Any) -> bool:
@@ -118,9 +121,10 @@ def lint(paths: List[str]) -> int:
     return 1 if bad else 0
 
 
-async def _execute(spec: Dict[str, Any], name: str) -> Dict[str, Any]:
+async def _execute(spec: Dict[str, Any], name: str,
+                   logs: Optional[LogStore] = None) -> Dict[str, Any]:
     client = MemoryClient(MemoryApiServer())
-    engine = LocalWorkflowEngine(client, ttl_seconds=None)
+    engine = LocalWorkflowEngine(client, ttl_seconds=None, logs=logs)
     sub = client.watch(WF_API_VERSION, WF_KIND, "local")
     await engine.start()
     try:
@@ -162,7 +166,28 @@ def _print_nodes(status: Dict[str, Any]) -> None:
         print(f"{name:<{width}}  {type_:<9}  {phase:<9}  {message}".rstrip())
 
 
-def run(path: str, params: List[str], remedy: bool) -> int:
+async def _execute_with_logs(spec: Dict[str, Any], name: str) -> Tuple[Dict[str, Any], bytes]:
+    """``_execute`` over a temporary log store; also returns the log of
+    every Pod node, in start order, under a ``--- displayName ---`` line."""
+    logs = LogStore()
+    try:
+        status = await _execute(spec, name, logs)
+        out: List[bytes] = []
+        for node in (status.get("nodes") or {}).values():
+            if node.get("type") != "Pod" or not logs.has_run("local", name):
+                continue
+            out.append(f"--- {node['displayName']} ---\n".encode())
+            try:
+                text = b"".join([c async for c in logs.read("local", name, node["id"])])
+            except NotFoundError:
+                text = b""
+            out.append(text if not text or text.endswith(b"\n") else text + b"\n")
+        return status, b"".join(out)
+    finally:
+        logs.close()
+
+
+def run(path: str, params: List[str], remedy: bool, logs: bool = False) -> int:
     wanted = "(remedyworkflow)" if remedy else "(workflow)"
     found: List[Tuple[str, Dict[str, Any]]] = []
     for label, spec, problems in _specs(path):
@@ -192,13 +217,21 @@ def run(path: str, params: List[str], remedy: bool) -> int:
         declared = [q for q in args.get("parameters") or []
                     if isinstance(q, dict) and q.get("name") not in overrides]
         args["parameters"] = declared + [{"name": k, "value": v} for k, v in overrides.items()]
-    status = asyncio.run(_execute(chosen, "run"))
+    log_text = b""
+    if logs:
+        status, log_text = asyncio.run(_execute_with_logs(chosen, "run"))
+    else:
+        status = asyncio.run(_execute(chosen, "run"))
     print(f"phase: {status['phase']}")
     if status.get("message"):
         print(f"message: {status['message']}")
     for p in (status.get("outputs") or {}).get("parameters") or []:
         print(f"output {p['name']}: {p['value']}")
     _print_nodes(status)
+    if log_text:
+        sys.stdout.flush()
+        sys.stdout.buffer.write(log_text)
+        sys.stdout.buffer.flush()
     return 0 if status["phase"] == "Succeeded" else 1
 
 
@@ -216,10 +249,12 @@ def main(argv: Optional[List[str]] = None) -> int:
                        help="set or override a spec.arguments parameter")
     p_run.add_argument("--remedy", action="store_true",
                        help="for a HealthCheck, run its remedy workflow instead of the check")
+    p_run.add_argument("--logs", action="store_true",
+                       help="after the node table, print what each leaf printed")
     args = ap.parse_args(argv)
     if args.cmd == "lint":
         return lint(args.files)
-    return run(args.file, args.parameter, args.remedy)
+    return run(args.file, args.parameter, args.remedy, args.logs)
 
 
 if __name__ == "__main__":

@@ -119,6 +119,8 @@ class _EngineBase:
             wf = ev["object"]
             if self._recovered and self._taken_at_start(ev["type"], wf):
                 continue
+            if ev["type"] == "DELETED":
+                self._deleted(wf)
             if ev["type"] != "ADDED":
                 continue
             if (wf.get("status") or {}).get("phase") in ("Succeeded", "Failed"):
@@ -138,6 +140,9 @@ class _EngineBase:
         except (TypeError, ValueError):
             pass  # opaque resourceVersion: keep matching by uid
         return ev_type == "ADDED" and meta.get("uid") in self._recovered
+
+    def _deleted(self, wf: Dict[str, Any]) -> None:
+        """The Workflow is gone: TTL, owner cascade or a user's delete."""
 
     def _spawn(self, wf: Dict[str, Any], coro: Any) -> None:
         key = f'{(wf["metadata"].get("namespace", ""))}/{wf["metadata"]["name"]}'
@@ -233,9 +238,10 @@ class _EngineBase:
         ):
             self._ttl_handles.popleft()
 
-    async def _set_status(self, wf: Dict[str, Any], status: Dict[str, Any]) -> None:
+    async def _set_status(self, wf: Dict[str, Any], status: Dict[str, Any]) -> bool:
         """Write the Workflow status the way the Argo controller does (the
-        Workflow CRD has no status subresource — a plain update)."""
+        Workflow CRD has no status subresource — a plain update). False when
+        the Workflow is gone."""
         meta = wf["metadata"]
         for _ in range(5):
             try:
@@ -243,13 +249,14 @@ class _EngineBase:
                     WF_API_VERSION, WF_KIND, meta.get("namespace", ""), meta["name"]
                 )
             except NotFoundError:
-                return
+                return False
             fresh["status"] = status
             try:
                 await self.client.update(fresh)
-                return
+                return True
             except ConflictError:
                 await asyncio.sleep(0.005)
+        return True
 
 
 class ScriptedWorkflowEngine(_EngineBase):
@@ -328,9 +335,17 @@ class LocalWorkflowEngine(_EngineBase):
 
     def __init__(self, client: KubeClient, namespace: Optional[str] = None,
                  ttl_seconds: Optional[float] = _EngineBase.DEFAULT_TTL,
-                 recover: bool = False):
+                 recover: bool = False, logs: Any = None):
         super().__init__(client, namespace, ttl_seconds, recover)
         self.completed = 0
+        #: a :class:`~.logs.LogStore` for what the leaves print, or None;
+        #: whoever built it closes it
+        self.logs = logs
+
+    def _deleted(self, wf: Dict[str, Any]) -> None:
+        if self.logs is not None:
+            meta = wf["metadata"]
+            self.logs.discard(meta.get("namespace", ""), meta["name"])
 
     async def stop(self) -> None:
         inflight = list(self._inflight.values())
@@ -344,6 +359,15 @@ class LocalWorkflowEngine(_EngineBase):
         from .validate import validate_workflow_spec
 
         spec = wf.get("spec") or {}
+        meta = wf["metadata"]
+        ns, name = meta.get("namespace", ""), meta["name"]
+        logs = self.logs
+        if logs is not None:
+            try:
+                logs.start_run(ns, name)
+            except (OSError, ValueError) as e:
+                log.warning("no logs kept for workflow %s/%s: %s", ns, name, e)
+                logs = None
         await self._set_status(wf, {"phase": "Running", "startedAt": _now_iso()})
         nodes: Dict[str, Any] = {}
         outputs: List[Dict[str, Any]] = []
@@ -351,12 +375,13 @@ class LocalWorkflowEngine(_EngineBase):
         if problems:
             phase, message = "Failed", problems[0]
         else:
-            meta = wf["metadata"]
-            run = WorkflowRun(spec, meta["name"], meta.get("namespace", ""))
+            run = WorkflowRun(spec, name, ns, logs=logs)
             try:
                 phase, message, timed_out = await self._run_phases(run, spec)
             except asyncio.CancelledError:
                 run.terminate("engine stopped")
+                if logs is not None:
+                    logs.finish_run(ns, name)
                 raise
             nodes = run.nodes
             if not timed_out:  # a run that was cut short publishes no outputs
@@ -368,7 +393,16 @@ class LocalWorkflowEngine(_EngineBase):
             status["outputs"] = {"parameters": outputs}
         if nodes:
             status["nodes"] = nodes
-        await self._set_status(wf, status)
+        exists = True
+        try:
+            exists = await self._set_status(wf, status)
+        finally:
+            if logs is not None:
+                logs.finish_run(ns, name)
+                if not exists:
+                    # deleted while it ran: its DELETED event came before
+                    # the last nodes wrote
+                    logs.discard(ns, name)
         self._schedule_ttl(wf)
         self.completed += 1
 

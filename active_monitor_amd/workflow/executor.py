@@ -8,6 +8,7 @@ writes; everything between the two writes happens here.
 from __future__ import annotations
 
 import asyncio
+import logging
 import os
 import shutil
 import signal
@@ -31,6 +32,20 @@ from .validate import task_dependencies
 
 #: ``outputs.result`` keeps at most this many bytes of a leaf's stdout
 RESULT_MAX_BYTES = 64 * 1024
+#: a failed leaf's message ends with this many characters of its output
+MESSAGE_TAIL_CHARS = 500
+#: bytes of each stream's end kept for that message: a character is at most
+#: four bytes, and a decoder that starts inside one is back in step within
+#: three more, so the last MESSAGE_TAIL_CHARS characters of the kept bytes
+#: are those of the whole stream
+_TAIL_BYTES = 4 * MESSAGE_TAIL_CHARS + 8
+#: one read of a leaf's pipe takes at most this much
+_PIPE_CHUNK = 64 * 1024
+#: after its group was killed a leaf's pipes reach EOF at once, unless a
+#: process that left the group still holds them; it is not waited for longer
+_KILL_DRAIN_SECONDS = 1.0
+
+log = logging.getLogger("active_monitor_amd.workflow")
 
 Scope = Dict[str, str]
 Outputs = Dict[str, Any]  # {"result": str, "parameters": {name: value}}
@@ -45,9 +60,14 @@ def _now_iso() -> str:
 
 
 class WorkflowRun:
-    def __init__(self, spec: Dict[str, Any], name: str, namespace: str):
+    def __init__(self, spec: Dict[str, Any], name: str, namespace: str,
+                 logs: Any = None):
         self.spec = spec
         self.name = name
+        self.namespace = namespace
+        #: a :class:`~.logs.LogStore`, or None: leaf output is then drained
+        #: and dropped
+        self.logs = logs
         self.templates = {t.get("name"): t for t in spec.get("templates") or []}
         self.nodes: Dict[str, Dict[str, Any]] = {}
         self.global_outputs: List[Dict[str, str]] = []
@@ -213,7 +233,7 @@ class WorkflowRun:
                 await asyncio.sleep(parse_duration(duration))
                 ok, message = True, ""
             elif "container" in tmpl or "script" in tmpl:
-                ok, message, outputs = await self._run_leaf(tmpl, scope)
+                ok, message, outputs = await self._run_leaf(tmpl, scope, node)
             else:
                 ok, message = False, "unsupported template type"
             if ok and type_ in ("Steps", "DAG"):
@@ -381,7 +401,8 @@ class WorkflowRun:
 
     # -- leaves -----------------------------------------------------------
 
-    async def _run_leaf(self, tmpl: Dict[str, Any], scope: Scope) -> Tuple[bool, str, Optional[Outputs]]:
+    async def _run_leaf(self, tmpl: Dict[str, Any], scope: Scope,
+                        node: Dict[str, Any]) -> Tuple[bool, str, Optional[Outputs]]:
         stdin: Optional[bytes] = None
         if "container" in tmpl:
             body = tmpl["container"] or {}
@@ -412,7 +433,7 @@ class WorkflowRun:
         )
         workdir = tempfile.mkdtemp(prefix="am-wf-") if needs_dir else None
         try:
-            ok, message, stdout = await self._exec(cmd, stdin, env, workdir)
+            ok, message, stdout = await self._exec(cmd, stdin, env, workdir, node)
             if not ok:
                 return False, message, None
             params: Dict[str, str] = {}
@@ -447,10 +468,26 @@ class WorkflowRun:
             if workdir is not None:
                 shutil.rmtree(workdir, ignore_errors=True)
 
+    def _log_writer(self, node: Optional[Dict[str, Any]]) -> Any:
+        """The log writer of a Pod node, or None: without a store, or when
+        the store cannot take this run (the leaf runs all the same)."""
+        if self.logs is None or node is None:
+            return None
+        try:
+            return self.logs.writer(self.namespace, self.name, node["id"],
+                                    node["displayName"])
+        except (OSError, ValueError) as e:
+            log.warning("no log kept for %s/%s node %s: %s",
+                        self.namespace, self.name, node["id"], e)
+            return None
+
     async def _exec(self, cmd: List[str], stdin: Optional[bytes], env: Optional[Dict[str, str]],
-                    cwd: Optional[str]) -> Tuple[bool, str, bytes]:
+                    cwd: Optional[str],
+                    node: Optional[Dict[str, Any]] = None) -> Tuple[bool, str, bytes]:
         """Run one process in a session of its own, so that the whole group
-        — shells and whatever they started — can be killed on cancellation."""
+        — shells and whatever they started — can be killed on cancellation.
+        Its output goes to the node's log as it is read; what is returned is
+        the first ``RESULT_MAX_BYTES`` of stdout."""
         spawn = asyncio.ensure_future(asyncio.create_subprocess_exec(
             *cmd,
             stdin=asyncio.subprocess.PIPE if stdin is not None else None,
@@ -474,21 +511,85 @@ class WorkflowRun:
         except (OSError, ValueError) as e:
             return False, str(e), b""
         self._procs[proc.pid] = proc
+        writer = self._log_writer(node)
+        out = _Kept(RESULT_MAX_BYTES)
+        err = _Kept(0)
+        pumps = [
+            asyncio.ensure_future(_pump(proc.stdout, out, writer)),
+            asyncio.ensure_future(_pump(proc.stderr, err, writer)),
+        ]
+        if stdin is not None:
+            pumps.append(asyncio.ensure_future(_feed(proc.stdin, stdin)))
+        # shielded: a cancellation must not stop the pumps before the kill,
+        # they still have to read what the group wrote until then
+        drained = asyncio.gather(*pumps)
+        drained.add_done_callback(lambda f: f.cancelled() or f.exception())
         try:
-            out, err = await proc.communicate(stdin)
+            # both pipes at EOF (every holder of them gone), then the leader
+            await asyncio.shield(drained)
+            await proc.wait()
         except BaseException:
             _kill_group(proc)
             try:
                 await proc.wait()
+                await asyncio.wait([drained], timeout=_KILL_DRAIN_SECONDS)
             except asyncio.CancelledError:
                 pass
             raise
         finally:
             self._procs.pop(proc.pid, None)
+            drained.cancel()
+            if writer is not None:
+                writer.close()
         if proc.returncode != 0:
-            tail = (err or out or b"").decode(errors="replace")[-500:]
-            return False, f"exit code {proc.returncode}: {tail}", out
-        return True, "", out
+            tail = (err.tail or out.tail).decode(errors="replace")[-MESSAGE_TAIL_CHARS:]
+            return False, f"exit code {proc.returncode}: {tail}", out.head
+        return True, "", out.head
+
+
+class _Kept:
+    """What of one stream stays in memory: its first ``head_max`` bytes and
+    its last ``_TAIL_BYTES``."""
+
+    __slots__ = ("head", "head_max", "tail")
+
+    def __init__(self, head_max: int):
+        self.head = b""
+        self.head_max = head_max
+        self.tail = b""
+
+    def add(self, chunk: bytes) -> None:
+        if len(self.head) < self.head_max:
+            self.head += chunk[:self.head_max - len(self.head)]
+        if len(chunk) >= _TAIL_BYTES:
+            self.tail = chunk[-_TAIL_BYTES:]
+        else:
+            self.tail = (self.tail + chunk)[-_TAIL_BYTES:]
+
+
+async def _pump(stream: "asyncio.StreamReader", kept: _Kept, writer: Any) -> None:
+    """Drain one pipe to EOF, a chunk at a time."""
+    while True:
+        chunk = await stream.read(_PIPE_CHUNK)
+        if not chunk:
+            return
+        kept.add(chunk)
+        if writer is not None:
+            writer.write(chunk)
+
+
+async def _feed(stdin: "asyncio.StreamWriter", data: bytes) -> None:
+    """Write a script to its interpreter and close the pipe; one that does
+    not read all of it is no error."""
+    try:
+        stdin.write(data)
+        await stdin.drain()
+    except (BrokenPipeError, ConnectionResetError):
+        pass
+    try:
+        stdin.close()
+    except (BrokenPipeError, ConnectionResetError):
+        pass
 
 
 def _kill_group(proc: "asyncio.subprocess.Process") -> None:
