@@ -19,6 +19,7 @@ from __future__ import annotations
 import argparse
 import asyncio
 import logging
+import os
 import sys
 from typing import Optional, Tuple
 
@@ -88,6 +89,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="memory backend: store HealthChecks as given instead "
                         "of validating and pruning them by the CRD schema "
                         "(also: AM_SCHEMA_VALIDATION=0 in the environment)")
+    p.add_argument("--cron-time-zone", metavar="ZONE",
+                   default=os.environ.get("AM_CRON_TIME_ZONE") or None,
+                   help="zone whose wall clock cron schedules without a TZ=/"
+                        "CRON_TZ= prefix are read on, e.g. Europe/Berlin "
+                        "(default, or 'Local': the controller's own clock; "
+                        "also: AM_CRON_TIME_ZONE in the environment)")
     add_log_flags(p)
     p.add_argument("--shard-index", type=int, default=0,
                    help="this controller's shard (keyspace split by CR-name hash)")
@@ -201,6 +208,7 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         shard_lease_duration=args.shard_lease_duration,
         shard_renew_interval=args.shard_renew_interval,
         metrics_security=metrics_security,
+        cron_time_zone=args.cron_time_zone,
     )
 
     stop = stop_on_signals(stop_event if stop_event is not None else asyncio.Event())
@@ -255,6 +263,13 @@ def main(argv=None) -> int:
         if given and args.backend != "memory":
             parser.error(f"{flag} applies to --backend memory only")
     check_log_flags(parser, args)
+    if args.cron_time_zone:
+        from ..engine.cronx import CronParseError, load_zone
+
+        try:
+            load_zone(args.cron_time_zone)
+        except CronParseError as e:
+            parser.error(f"--cron-time-zone: {e}")
     try:
         return asyncio.run(run(args))
     except KeyboardInterrupt:

@@ -1,6 +1,12 @@
 """Controller runtime: workqueue, manager, reconciler, cron, backoff, RBAC."""
 from .backoff import IEBTimeoutError, InverseExponentialBackoff, compute_backoff_params
-from .cronx import CronParseError, parse_go_duration, parse_standard, seconds_until_next
+from .cronx import (
+    CronParseError,
+    load_zone,
+    parse_go_duration,
+    parse_standard,
+    seconds_until_next,
+)
 from .manager import Manager
 from .parse import (
     WorkflowParseError,
@@ -32,6 +38,7 @@ __all__ = [
     "WorkQueue",
     "WorkflowParseError",
     "compute_backoff_params",
+    "load_zone",
     "parse_go_duration",
     "parse_remedy_workflow_from_healthcheck",
     "parse_remedy_workflow_from_healthcheck_async",

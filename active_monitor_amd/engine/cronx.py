@@ -12,14 +12,19 @@ implementation of the same accepted grammar:
 - descriptors ``@yearly|@annually``, ``@monthly``, ``@weekly``,
   ``@daily|@midnight``, ``@hourly``, and ``@every <go-duration>``,
 - classic dom/dow union rule: when BOTH day fields are restricted, a time
-  matches if EITHER matches.
+  matches if EITHER matches,
+- an optional leading ``TZ=<zone>`` or ``CRON_TZ=<zone>``: the fields are then
+  read on that zone's wall clock, daylight-saving changes included (a wall
+  time a spring-forward skips does not fire that day, one a fall-back repeats
+  fires twice). The rule follows robfig/cron's documented behaviour.
 """
 from __future__ import annotations
 
 import re
 from dataclasses import dataclass
-from datetime import datetime, timedelta, timezone
-from typing import FrozenSet, Optional, Tuple
+from datetime import datetime, timedelta, timezone, tzinfo
+from typing import FrozenSet, Optional, Tuple, Union
+from zoneinfo import ZoneInfo
 
 
 class CronParseError(ValueError):
@@ -50,6 +55,11 @@ _DESCRIPTORS = {
     "@midnight": "0 0 * * *",
     "@hourly": "0 * * * *",
 }
+
+_TZ_PREFIXES = ("TZ=", "CRON_TZ=")  # robfig's spellings, case-sensitive
+
+#: longest single jump of the zone-aware search (see ``_next_in_zone``)
+_MAX_JUMP = timedelta(days=7)
 
 _GO_DURATION_RE = re.compile(r"(\d+(?:\.\d*)?|\.\d+)(ns|us|µs|μs|ms|s|m|h)")
 _GO_UNIT_SECONDS = {
@@ -147,6 +157,9 @@ class Schedule:
     dom_star: bool
     dow_star: bool
     every: Optional[float] = None  # seconds, for @every schedules
+    #: the zone whose wall clock the fields are read on (TZ=/CRON_TZ= prefix
+    #: or a default); None reads them on ``after``'s own clock
+    zone: Optional[tzinfo] = None
 
     def _day_matches(self, t: datetime) -> bool:
         dom_ok = t.day in self.dom
@@ -164,6 +177,8 @@ class Schedule:
         if self.every is not None:
             # @every d: constant interval from 'after', truncated to seconds
             return after + timedelta(seconds=self.every)
+        if self.zone is not None:
+            return self._next_in_zone(after)
         t = after.replace(second=0, microsecond=0) + timedelta(minutes=1)
         limit = t + timedelta(days=5 * 366)
         while t < limit:
@@ -186,13 +201,98 @@ class Schedule:
             return t
         raise CronParseError("no activation time within five years")
 
+    def _next_in_zone(self, after: datetime) -> datetime:
+        """The earliest whole-minute instant strictly after ``after`` whose
+        wall-clock fields, read in ``self.zone``, match; returned in
+        ``after``'s tzinfo.
 
-def parse_standard(spec: str) -> Schedule:
+        The search walks instants (UTC) forward and reads the wall clock only
+        where a candidate is tested. A mismatching month, day or hour is
+        skipped in one jump to the wall-clock start of the next one, as in
+        the zone-less search. A jump assumes the offset holds; when the
+        offset at the landing differs, a transition lies on the way and the
+        search lands on the transition instead, so a wall time that a gap
+        skips is never produced and one that a fold repeats is seen twice.
+        Jumps are at most a week long: two offset changes that cancel would
+        have to lie within one week to go unseen."""
+        if after.tzinfo is None or after.utcoffset() is None:
+            raise ValueError("a schedule with a time zone needs a timezone-aware time")
+        zone = self.zone
+        t = after.astimezone(timezone.utc).replace(second=0, microsecond=0)
+        t += timedelta(minutes=1)
+        limit = t + timedelta(days=5 * 366)
+        while t < limit:
+            local = t.astimezone(zone)
+            w = local.replace(tzinfo=None)  # wall clock at t
+            if w.month not in self.months:
+                if w.month == 12:
+                    target = w.replace(year=w.year + 1, month=1, day=1, hour=0, minute=0)
+                else:
+                    target = w.replace(month=w.month + 1, day=1, hour=0, minute=0)
+                target = min(target, (w + _MAX_JUMP).replace(hour=0, minute=0))
+            elif not self._day_matches(w):
+                target = (w + timedelta(days=1)).replace(hour=0, minute=0)
+            elif w.hour not in self.hours:
+                target = (w + timedelta(hours=1)).replace(minute=0)
+            elif w.minute not in self.minutes:
+                t += timedelta(minutes=1)
+                continue
+            else:
+                return t.astimezone(after.tzinfo)
+            # every wall time in [w, target) shares the mismatching field
+            offset = local.utcoffset()
+            landing = t + (target - w)
+            if landing.astimezone(zone).utcoffset() != offset:
+                # first whole minute in (t, landing] with another offset
+                lo, hi = 0, int((landing - t).total_seconds() // 60)
+                while hi - lo > 1:
+                    mid = (lo + hi) // 2
+                    if (t + timedelta(minutes=mid)).astimezone(zone).utcoffset() == offset:
+                        lo = mid
+                    else:
+                        hi = mid
+                landing = t + timedelta(minutes=hi)
+            t = landing
+        raise CronParseError("no activation time within five years")
+
+
+def load_zone(name: str) -> Optional[tzinfo]:
+    """Resolve a zone name the way robfig's ``time.LoadLocation`` call does:
+    ``UTC`` and the empty name are UTC, ``Local`` is no zone (None), anything
+    else is looked up in the zone database. An unknown or malformed name is a
+    ``CronParseError`` reading ``provided bad location <name>``."""
+    if name in ("", "UTC"):
+        return ZoneInfo("UTC")
+    if name == "Local":
+        return None
+    try:
+        return ZoneInfo(name)
+    except (KeyError, ValueError, OSError) as e:
+        # ZoneInfoNotFoundError is a KeyError; a path-like key ("../x") is a
+        # ValueError; a directory of the database ("America") an OSError
+        raise CronParseError(f"provided bad location {name}: {e}") from None
+
+
+def _as_zone(zone: Union[None, str, tzinfo]) -> Optional[tzinfo]:
+    return load_zone(zone) if isinstance(zone, str) else zone
+
+
+def parse_standard(spec: str, default_zone: Union[None, str, tzinfo] = None) -> Schedule:
     """Parse a standard 5-field cron expression or descriptor
-    (robfig/cron ParseStandard equivalent)."""
+    (robfig/cron ParseStandard equivalent), with an optional leading
+    ``TZ=<zone>`` / ``CRON_TZ=<zone>``. ``default_zone`` (a zone name or a
+    tzinfo) applies only when the spec carries no such prefix."""
     spec = spec.strip()
     if not spec:
         raise CronParseError("empty spec string")
+    if spec.startswith(_TZ_PREFIXES):
+        parts = spec.split(None, 1)  # the zone name runs to the first whitespace
+        if len(parts) < 2:
+            raise CronParseError(f"time zone prefix without a schedule: {spec!r}")
+        zone = load_zone(parts[0].partition("=")[2])
+        spec = parts[1].strip()
+    else:
+        zone = _as_zone(default_zone)
     if spec.startswith("@every "):
         secs = parse_go_duration(spec[len("@every "):])
         if secs <= 0:
@@ -218,18 +318,25 @@ def parse_standard(spec: str) -> Schedule:
     (mins, _), (hrs, _), (dom, dom_star), (months, _), (dow, dow_star) = parsed
     return Schedule(
         minutes=mins, hours=hrs, dom=dom, months=months, dow=dow,
-        dom_star=dom_star, dow_star=dow_star,
+        dom_star=dom_star, dow_star=dow_star, zone=zone,
     )
 
 
-def seconds_until_next(spec: str, now: Optional[datetime] = None) -> int:
+def seconds_until_next(
+    spec: str,
+    now: Optional[datetime] = None,
+    default_zone: Union[None, str, tzinfo] = None,
+) -> int:
     """The reference's cron→RepeatAfterSec derivation:
     ``int(next - now) + 1`` seconds, the +1 compensating integer truncation
     (healthcheck_controller.go:251-263)."""
+    sched = parse_standard(spec, default_zone)
     if now is None:
-        # local time, like robfig's default Schedule.Next(time.Now()) — an
-        # operator writing "0 9 * * *" means 9am on the controller's clock
-        now = datetime.now().astimezone()
-    sched = parse_standard(spec)
+        if sched.zone is not None:
+            now = datetime.now(timezone.utc)
+        else:
+            # local time, like robfig's default Schedule.Next(time.Now()) — an
+            # operator writing "0 9 * * *" means 9am on the controller's clock
+            now = datetime.now().astimezone()
     delta = (sched.next(now) - now).total_seconds()
     return int(delta) + 1

@@ -155,6 +155,7 @@ async def _handle(reader: asyncio.StreamReader, writer: asyncio.StreamWriter,
                     "completed_runs": getattr(rec, "completed_runs", 0),
                     "active_watches": rec.active_watches() if rec else 0,
                     "armed_timers": len(getattr(rec, "repeat_timers_by_name", {})),
+                    "cron_time_zone": getattr(rec, "cron_time_zone", None),
                     "apiserver_requests": getattr(
                         getattr(manager, "client", None), "request_count", None
                     ),

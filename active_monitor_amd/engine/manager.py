@@ -55,6 +55,7 @@ class Manager:
         shard_lease_duration: float = 15.0,
         shard_renew_interval: float = 5.0,
         resync_period: float = 10 * 3600.0,
+        cron_time_zone: Optional[str] = None,
     ):
         self.client = client
         self.max_workers = max_workers
@@ -62,7 +63,8 @@ class Manager:
         self.queue = WorkQueue()
         self.recorder = recorder or EventRecorder(client)
         self.reconciler = HealthCheckReconciler(
-            client, self.recorder, max_parallel=max_workers, queue=self.queue
+            client, self.recorder, max_parallel=max_workers, queue=self.queue,
+            cron_time_zone=cron_time_zone,
         )
         self.metrics_addr = metrics_addr
         self.health_addr = health_addr

@@ -46,7 +46,7 @@ from ..metrics import (
     create_dynamic_prometheus_metric,
 )
 from .backoff import IEBTimeoutError, InverseExponentialBackoff, compute_backoff_params
-from .cronx import CronParseError, seconds_until_next
+from .cronx import CronParseError, load_zone, seconds_until_next
 from .parse import parse_from_healthcheck_async
 from .rbac import RBACProvisioner
 from .workqueue import WorkQueue
@@ -92,6 +92,7 @@ class HealthCheckReconciler:
         recorder: EventRecorder,
         max_parallel: int = 10,
         queue: Optional[WorkQueue] = None,
+        cron_time_zone: Optional[str] = None,
     ):
         self.client = client
         self.recorder = recorder
@@ -99,6 +100,11 @@ class HealthCheckReconciler:
         # NB: not `queue or WorkQueue()` — an empty WorkQueue is falsy (__len__)
         self.queue = queue if queue is not None else WorkQueue()
         self.rbac = RBACProvisioner(client, recorder)
+        # zone for cron schedules that carry no TZ=/CRON_TZ= prefix; None (or
+        # "Local") reads them on the controller's own clock. A bad name
+        # raises CronParseError here, at start-up, not per CR later.
+        self.cron_time_zone = cron_time_zone if cron_time_zone != "Local" else None
+        self._cron_zone = load_zone(cron_time_zone) if cron_time_zone else None
         # optional WorkflowWatchHub (set by the Manager): event-driven wakeups
         # for workflow completion; None falls back to pure IEB polling
         self.wf_hub = None
@@ -347,8 +353,12 @@ class HealthCheckReconciler:
         if spec.repeat_after_sec <= 0:
             # cron branch (:251-263): +1s compensates integer truncation
             try:
-                spec.repeat_after_sec = seconds_until_next(spec.schedule.cron)
-            except CronParseError:
+                spec.repeat_after_sec = seconds_until_next(
+                    spec.schedule.cron, default_zone=self._cron_zone
+                )
+            except CronParseError as e:
+                log.warning("healthcheck %s: fail to parse cron %r: %s",
+                            hc.name, spec.schedule.cron, e)
                 await self._event(hc, "Warning", "Fail to parse cron")
                 raise
         # already executed recently and a repeat is scheduled (:264-267). The
@@ -730,7 +740,7 @@ class HealthCheckReconciler:
         cron = ((fresh_spec.get("schedule") or {}).get("cron")) or ""
         if int(fresh_spec.get("repeatAfterSec", 0) or 0) <= 0 and cron:
             try:
-                repeat_after_sec = seconds_until_next(cron)
+                repeat_after_sec = seconds_until_next(cron, default_zone=self._cron_zone)
             except CronParseError:
                 pass  # keep the submit-time value
         self._arm_repeat_timer(hc.name, hc.namespace, repeat_after_sec)

@@ -4,9 +4,10 @@
     Check Workflow or HealthCheck YAML against the surface the local executor
     supports. A HealthCheck is first held against the CRD schema the way a
     strict ``apply`` would (``invalid HealthCheck: spec.repeatAfterSec: ...``,
-    ``invalid HealthCheck: unknown field "spec.x"``); then its inline check
-    and remedy workflows are linted. Prints one line per problem; exit status
-    1 when there are any.
+    ``invalid HealthCheck: unknown field "spec.x"``); a cron schedule the
+    controller would use is parsed (``invalid HealthCheck: spec.schedule.cron:
+    ...``); then its inline check and remedy workflows are linted. Prints one
+    line per problem; exit status 1 when there are any.
 
 ``run FILE [-p name=value ...] [--remedy] [--logs]``
     Execute one workflow with the local executor against a throw-away
@@ -15,18 +16,28 @@
     adds what every leaf printed, stdout and stderr, under a ``--- NODE ---``
     line each. Exit status 0 for ``Succeeded``, 1 for ``Failed``.
 
-Neither needs a server.
+``next (FILE | --cron SPEC) [-n N] [--from RFC3339] [--time-zone ZONE]``
+    Print the next N (default 5) activations of a cron schedule, one per
+    line: the instant in the schedule's zone, the same instant in UTC, and
+    the ``RepeatAfterSec`` the controller would derive at ``--from`` (default
+    now). For a FILE, every HealthCheck's ``spec.schedule.cron`` is shown.
+    ``--time-zone`` plays the role of the controller's ``--cron-time-zone``.
+    A schedule that does not parse prints ``error: ...``; exit status 1.
+
+None of them needs a server.
 """
 from __future__ import annotations
 
 import argparse
 import asyncio
 import sys
+from datetime import datetime, timezone
 from typing import Any, Dict, Iterator, List, Optional, Tuple
 
 import yaml
 
 from ..api.types import HealthCheck
+from ..engine.cronx import CronParseError, parse_standard
 from ..engine.parse import (
     WorkflowParseError,
     parse_remedy_workflow_from_healthcheck,
@@ -87,6 +98,12 @@ def _specs(path: str) -> Iterator[Tuple[str, Optional[Dict[str, Any]], List[str]
             except Exception as e:
                 yield label, None, [f"invalid HealthCheck: {e}"]
                 continue
+            if hc.spec.repeat_after_sec <= 0 and hc.spec.schedule.cron:
+                try:
+                    parse_standard(hc.spec.schedule.cron)
+                except CronParseError as e:
+                    yield label, None, [f"invalid HealthCheck: spec.schedule.cron: {e}"]
+                    continue
             found = False
             for what, wf, parse in (
                 ("workflow", hc.spec.workflow, parse_workflow_from_healthcheck),
@@ -235,6 +252,52 @@ def run(path: str, params: List[str], remedy: bool, logs: bool = False) -> int:
     return 0 if status["phase"] == "Succeeded" else 1
 
 
+def _crons(path: str) -> List[Tuple[str, str]]:
+    """``(label, spec.schedule.cron)`` for every HealthCheck in ``path``."""
+    with open(path) as f:
+        docs = [d for d in yaml.safe_load_all(f) if isinstance(d, dict)]
+    out = []
+    for doc in docs:
+        if doc.get("kind") != "HealthCheck":
+            continue
+        name = (doc.get("metadata") or {}).get("name") or path
+        cron = ((doc.get("spec") or {}).get("schedule") or {}).get("cron")
+        if not cron:
+            raise CronParseError(f"{name}: no spec.schedule.cron")
+        out.append((name, str(cron)))
+    if not out:
+        raise CronParseError(f"{path}: no HealthCheck found")
+    return out
+
+
+def next_activations(path: Optional[str], cron: Optional[str], count: int,
+                     start: Optional[str], time_zone: Optional[str]) -> int:
+    try:
+        if start is None:
+            now = datetime.now(timezone.utc).replace(microsecond=0)
+        else:
+            now = datetime.fromisoformat(start[:-1] + "+00:00" if start[-1:] in "Zz" else start)
+            if now.tzinfo is None:
+                raise ValueError(f"--from needs a UTC offset or Z: {start!r}")
+        crons = [("", cron)] if cron is not None else _crons(path)
+        for label, spec in crons:
+            sched = parse_standard(spec, default_zone=time_zone)
+            # a schedule without any zone runs on the controller's own clock
+            t = now if sched.zone is not None else now.astimezone()
+            if label:
+                print(f"{label}: {spec}")
+            for _ in range(count):
+                nxt = sched.next(t)
+                shown = nxt.astimezone(sched.zone) if sched.zone is not None else nxt
+                print(f"{shown.isoformat()}  {nxt.astimezone(timezone.utc):%Y-%m-%dT%H:%M:%SZ}"
+                      f"  RepeatAfterSec={int((nxt - now).total_seconds()) + 1}")
+                t = nxt
+    except (OSError, ValueError, yaml.YAMLError) as e:  # CronParseError is a ValueError
+        print(f"error: {e}")
+        return 1
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(
         prog="python -m active_monitor_amd.workflow",
@@ -251,9 +314,24 @@ def main(argv: Optional[List[str]] = None) -> int:
                        help="for a HealthCheck, run its remedy workflow instead of the check")
     p_run.add_argument("--logs", action="store_true",
                        help="after the node table, print what each leaf printed")
+    p_next = sub.add_parser("next", help="print a cron schedule's next activations")
+    what = p_next.add_mutually_exclusive_group(required=True)
+    what.add_argument("file", nargs="?", metavar="FILE",
+                      help="HealthCheck YAML; its spec.schedule.cron is used")
+    what.add_argument("--cron", metavar="SPEC", help="a cron schedule, e.g. "
+                      "'CRON_TZ=Europe/Berlin 0 9 * * MON-FRI'")
+    p_next.add_argument("-n", type=int, default=5, metavar="N",
+                        help="how many activations (default 5)")
+    p_next.add_argument("--from", dest="start", default=None, metavar="RFC3339",
+                        help="start after this instant (default: now)")
+    p_next.add_argument("--time-zone", default=None, metavar="ZONE",
+                        help="zone for a schedule without a TZ=/CRON_TZ= prefix, "
+                             "as the controller's --cron-time-zone")
     args = ap.parse_args(argv)
     if args.cmd == "lint":
         return lint(args.files)
+    if args.cmd == "next":
+        return next_activations(args.file, args.cron, args.n, args.start, args.time_zone)
     return run(args.file, args.parameter, args.remedy, args.logs)
 
 
