@@ -145,6 +145,9 @@ async def _handle(reader: asyncio.StreamReader, writer: asyncio.StreamWriter,
             stats = {}
             if manager is not None:
                 rec = getattr(manager, "reconciler", None)
+                # the HealthCheck informer's subscription; only the HTTP
+                # backend's can expire and so has these counters
+                sub = getattr(manager, "_sub", None)
                 stats = {
                     "ready": manager.ready,
                     "workers": getattr(manager, "max_workers", None),
@@ -162,6 +165,8 @@ async def _handle(reader: asyncio.StreamReader, writer: asyncio.StreamWriter,
                     "owned_shards": sorted(
                         getattr(getattr(manager, "coordinator", None), "owned", ())
                     ),
+                    "watch_relists": getattr(sub, "relists", 0),
+                    "watch_synthetic_deletes": getattr(sub, "synthetic_deletes", 0),
                 }
             body, ctype, code = json.dumps(stats).encode(), "application/json", 200
         elif path.startswith("/healthz"):

@@ -44,6 +44,7 @@ from ..metrics import (
     MonitorStartedTime,
     MonitorSuccess,
     create_dynamic_prometheus_metric,
+    forget_healthcheck,
 )
 from .backoff import IEBTimeoutError, InverseExponentialBackoff, compute_backoff_params
 from .cronx import CronParseError, load_zone, seconds_until_next
@@ -123,6 +124,12 @@ class HealthCheckReconciler:
         self._written_rv: Dict[Tuple[str, str], int] = {}
         self.repeat_timers_by_name: Dict[Tuple[str, str], RepeatTimer] = {}
         self._watch_tasks: Dict[str, Set[asyncio.Task]] = {}
+        # uid of the object each key's run and timer were started for: a
+        # HealthCheck deleted and re-created under its name is another object
+        self._driven_uid: Dict[Tuple[str, str], str] = {}
+        # name -> namespaces whose check of that name has emitted metrics;
+        # the series carry the name alone, so they go with the last of them
+        self._metric_namespaces: Dict[str, Set[str]] = {}
         # observability for benchmarks/tests
         self.reconcile_count = 0
         self.completed_runs = 0
@@ -279,20 +286,42 @@ class HealthCheckReconciler:
         try:
             obj = await self._get_hc(namespace, name)
         except NotFoundError:
-            # CR deleted: stop the repeat timer so self-scheduling halts
-            # (:180-184); in-flight watches are cancelled proactively (the
-            # reference lets them die on workflow NotFound after GC).
-            if self.forget(namespace, name):
-                log.info("cancelled rescheduled workflow for deleted healthcheck %s", name)
-                await self.recorder.event(
-                    {"apiVersion": API_VERSION, "kind": HC_KIND,
-                     "metadata": {"name": name, "namespace": namespace}},
-                    "Normal", "Normal",
-                    "Cancelling workflow for this healthcheck due to deletion",
-                )
+            await self._deleted(namespace, name)
             return ReconcileResult()
+        driven = self._driven_uid.get((namespace, name))
+        if driven and driven != ((obj.get("metadata") or {}).get("uid") or driven):
+            # deleted and re-created before this key was reconciled in
+            # between (the queue holds a key once): what is held belongs to
+            # the old object and must not outlive it, nor may its in-flight
+            # run pass for a run of the new one
+            await self._deleted(namespace, name)
+            self._watch_tasks.pop((namespace, name), None)
         hc = HealthCheck.from_dict(obj)
         return await self._process_or_recover(hc, from_timer=TIMER_FLAG in flags)
+
+    async def _deleted(self, namespace: str, name: str) -> None:
+        """The CR is gone: stop the repeat timer so self-scheduling halts
+        (:180-184) and cancel the in-flight watches proactively (the
+        reference lets them die on workflow NotFound after GC) — first, so
+        that no late completion can re-create a series — then drop the
+        name's metric series once no namespace has a check of that name
+        left (the series are labelled by name alone, as in the reference)."""
+        stopped = self.forget(namespace, name)
+        self._driven_uid.pop((namespace, name), None)
+        spaces = self._metric_namespaces.get(name)
+        if spaces is not None:
+            spaces.discard(namespace)
+        if not spaces:
+            self._metric_namespaces.pop(name, None)
+            forget_healthcheck(name)
+        if stopped:
+            log.info("cancelled rescheduled workflow for deleted healthcheck %s", name)
+            await self.recorder.event(
+                {"apiVersion": API_VERSION, "kind": HC_KIND,
+                 "metadata": {"name": name, "namespace": namespace}},
+                "Normal", "Normal",
+                "Cancelling workflow for this healthcheck due to deletion",
+            )
 
     async def _process_or_recover(self, hc: HealthCheck, from_timer: bool) -> ReconcileResult:
         """Panic guard + error policy (reference :190-223). The reference's
@@ -380,6 +409,7 @@ class HealthCheckReconciler:
             raise
 
         generated_name = await self.create_submit_workflow(hc)
+        self._driven_uid[(hc.namespace, hc.name)] = hc.metadata.uid
         # non-blocking watch: the reconcile worker is freed immediately
         self._spawn_watch(
             (hc.namespace, hc.name),
@@ -625,6 +655,12 @@ class HealthCheckReconciler:
     # Status + metric mutations for a terminal workflow: check, then remedy
     # ------------------------------------------------------------------
 
+    def _note_metrics(self, hc: HealthCheck) -> None:
+        spaces = self._metric_namespaces.get(hc.name)
+        if spaces is None:
+            spaces = self._metric_namespaces[hc.name] = set()
+        spaces.add(hc.namespace)
+
     async def _apply_check_result(
         self, hc: HealthCheck, wf_name: str, status: Dict[str, Any],
         then: str, then_unix: float,
@@ -634,6 +670,7 @@ class HealthCheckReconciler:
         st = hc.status
         now = k8s_now()
         now_unix = time.time()
+        self._note_metrics(hc)
         if status.get("phase") == SUCC_STR:
             await self._event(hc, "Normal", "Workflow status is Succeeded")
             st.status = SUCC_STR
@@ -688,6 +725,7 @@ class HealthCheckReconciler:
         st = hc.status
         now = k8s_now()
         now_unix = time.time()
+        self._note_metrics(hc)
         if status.get("phase") == SUCC_STR:
             await self._event(hc, "Normal", "Remedy workflow status is Succeeded")
             st.remedy_status = SUCC_STR
@@ -803,13 +841,17 @@ class HealthCheckReconciler:
     # ------------------------------------------------------------------
 
     async def _get_live_hc(self, hc: HealthCheck) -> Optional[Dict[str, Any]]:
-        """Fresh read for a status write; None when the CR is gone or being
-        deleted, in which case nothing is written."""
+        """Fresh read for a status write; None when the CR is gone, being
+        deleted, or another object of the same name (deleted and re-created
+        while the run was in flight), in which case nothing is written."""
         try:
             fresh = await self._get_hc(hc.namespace, hc.name)
         except NotFoundError:
             return None
-        if (fresh.get("metadata") or {}).get("deletionTimestamp"):
+        meta = fresh.get("metadata") or {}
+        if meta.get("deletionTimestamp"):
+            return None
+        if hc.metadata.uid and meta.get("uid") and meta["uid"] != hc.metadata.uid:
             return None
         return fresh
 

@@ -102,14 +102,29 @@ class HttpSubscription:
     controller-runtime, healthcheck_controller.go:133-137):
 
     - a 410 Gone response or a watch ``ERROR`` event (code 410 or otherwise)
-      clears the stored resourceVersion, **re-lists** the collection —
-      emitting a synthetic ``ADDED`` per live object so consumers can't miss
-      changes that happened inside the expiry window — and resumes watching
-      from the list's resourceVersion,
+      clears the stored resourceVersion, **re-lists** the collection and
+      delivers the list as a *Replace*: first a synthetic ``DELETED`` for
+      every object the consumer was told about that the list no longer holds
+      (or holds under another uid: deleted and re-created inside the expiry
+      window), then a synthetic ``ADDED`` per live object — so consumers
+      miss neither the changes nor the deletions that happened inside the
+      window — and resumes watching from the list's resourceVersion,
     - ``allowWatchBookmarks`` is requested and BOOKMARK events advance the
       resume point without being delivered,
     - frames are read with an incremental buffer, so a watch event larger
       than aiohttp's 64 KB readline limit cannot wedge the stream.
+
+    For the Replace the subscription remembers what it has delivered, as
+    ``(namespace, name) -> uid``: identities only, never objects, so the
+    memory is proportional to the number of live objects. The first connect
+    carries no resourceVersion and the server replays the current state as
+    ``ADDED``, so the map is complete without a list of its own. The last
+    state of an object whose deletion was missed is therefore not known, and
+    a synthetic ``DELETED`` carries a tombstone instead (client-go's
+    ``DeletedFinalStateUnknown``): ``apiVersion``, ``kind`` and a ``metadata``
+    of ``namespace``, ``name``, ``uid`` and the list's ``resourceVersion``,
+    with a top-level ``"synthetic": true`` beside ``type`` and ``object``.
+    Consumers read only ``metadata`` of a ``DELETED`` event's object.
     """
 
     def __init__(self, client: "HttpClient", api_version: str, kind: str,
@@ -124,6 +139,10 @@ class HttpSubscription:
         self._task = asyncio.ensure_future(self._pump())
         #: test/telemetry counter: completed re-list recoveries
         self.relists = 0
+        #: synthetic DELETED events those re-lists produced
+        self.synthetic_deletes = 0
+        # what the consumer has been told exists: (namespace, name) -> uid
+        self._known: Dict[Tuple[str, str], str] = {}
         # a 401 on connect earns one immediate reconnect with a fresh
         # credential; re-armed by the next connect that is accepted
         self._auth_retry_armed = True
@@ -142,13 +161,18 @@ class HttpSubscription:
                     self.api_version, self.kind,
                 )
                 self._resource_version = None
-                try:
-                    await self._relist()
-                except asyncio.CancelledError:
-                    return
-                except Exception as e:
-                    log.warning("re-list after watch expiry failed: %s", e)
-                    await asyncio.sleep(1.0)
+                # retried until it succeeds: a connect without a
+                # resourceVersion would replay the live objects but, unlike
+                # the re-list, could not say which ones are gone
+                while not self._closed:
+                    try:
+                        await self._relist()
+                        break
+                    except asyncio.CancelledError:
+                        return
+                    except Exception as e:
+                        log.warning("re-list after watch expiry failed: %s", e)
+                        await asyncio.sleep(1.0)
             except _WatchUnauthorized as e:
                 if self._closed:
                     return
@@ -168,19 +192,43 @@ class HttpSubscription:
                 await asyncio.sleep(1.0)
 
     async def _relist(self) -> None:
-        """Reflector-style recovery: list the collection, surface every live
-        object as a synthetic ADDED (consumers treat events as level
-        triggers), and resume the watch from the list's resourceVersion."""
+        """Reflector-style recovery: list the collection, deliver it as a
+        Replace and resume the watch from the list's resourceVersion. The
+        deletions come first — a consumer must drop what it holds for an
+        object that was deleted and re-created before it sees the new one —
+        then every live object as a synthetic ADDED (consumers treat events
+        as level triggers)."""
         path = self._client._collection_path(self.api_version, self.kind, self.namespace)
         out = await self._client._request("GET", path)
+        if self._closed:
+            return
         rv = (out.get("metadata") or {}).get("resourceVersion")
         if rv:
             self._resource_version = str(rv)
-        for obj in out.get("items", []):
-            if self._closed:
-                return
+        items = out.get("items", [])
+        listed: Dict[Tuple[str, str], str] = {}
+        for obj in items:
+            meta = obj.get("metadata") or {}
+            listed[(meta.get("namespace", ""), meta.get("name", ""))] = meta.get("uid", "")
+        for key, uid in self._known.items():
+            if listed.get(key) != uid:
+                self._queue.put_nowait(self._tombstone(key, uid, rv))
+                self.synthetic_deletes += 1
+        for obj in items:
             self._queue.put_nowait({"type": "ADDED", "object": obj})
+        self._known = listed
         self.relists += 1
+
+    def _tombstone(self, key: Tuple[str, str], uid: str, rv: Any) -> Dict[str, Any]:
+        meta: Dict[str, Any] = {"namespace": key[0], "name": key[1], "uid": uid}
+        if rv:
+            meta["resourceVersion"] = str(rv)
+        return {
+            "type": "DELETED",
+            "object": {"apiVersion": self.api_version, "kind": self.kind,
+                       "metadata": meta},
+            "synthetic": True,
+        }
 
     #: server-side watch budget (client-go reflectors use 5-10 min): bounds
     #: how long a half-open TCP connection can silently starve the informer
@@ -241,13 +289,19 @@ class HttpSubscription:
             # a watch ERROR carries a metav1.Status; 410 (or anything else —
             # the stream is unusable either way) triggers re-list recovery
             raise _Expired()
-        rv = (obj.get("metadata") or {}).get("resourceVersion")
+        meta = obj.get("metadata") or {}
+        rv = meta.get("resourceVersion")
         if rv:
             self._resource_version = str(rv)
         if etype == "BOOKMARK":
             return  # resume-point advance only, never delivered
-        if etype in ("ADDED", "MODIFIED", "DELETED"):
-            self._queue.put_nowait({"type": etype, "object": obj})
+        if etype == "DELETED":
+            self._known.pop((meta.get("namespace", ""), meta.get("name", "")), None)
+        elif etype in ("ADDED", "MODIFIED"):
+            self._known[(meta.get("namespace", ""), meta.get("name", ""))] = meta.get("uid", "")
+        else:
+            return
+        self._queue.put_nowait({"type": etype, "object": obj})
 
     def close(self) -> None:
         self._closed = True

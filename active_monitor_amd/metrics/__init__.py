@@ -9,6 +9,7 @@ from .collector import (
     create_dynamic_prometheus_metric,
     custom_gauge_metrics,
     exposition,
+    forget_healthcheck,
 )
 
 __all__ = [
@@ -21,4 +22,5 @@ __all__ = [
     "create_dynamic_prometheus_metric",
     "custom_gauge_metrics",
     "exposition",
+    "forget_healthcheck",
 ]

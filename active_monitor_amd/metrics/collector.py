@@ -24,13 +24,18 @@ registered dynamically by :func:`create_dynamic_prometheus_metric`
 (collector.go:68-115) — and, unlike the reference (which documents the feature
 but never calls it — SURVEY.md §2.3, quirk list), the reconciler here invokes
 it on the workflow-success path.
+
+Series end with the HealthCheck they describe: :func:`forget_healthcheck`
+removes every label set of a name, static and dynamic. The reference never
+removes one (collector.go:55-60), so its ``/metrics`` grows with every
+HealthCheck that ever existed.
 """
 from __future__ import annotations
 
 import json
 import logging
 import threading
-from typing import Any, Dict, Iterable, List, Optional, Tuple
+from typing import Any, Dict, Iterable, List, Optional, Set, Tuple
 
 from prometheus_client import CollectorRegistry, Gauge, generate_latest
 from prometheus_client.core import Metric
@@ -72,6 +77,11 @@ class _ExactNameCounter:
         with self._lock:
             return self._values.get(tuple(labelvalues), 0.0)
 
+    def remove(self, *labelvalues: str) -> bool:
+        """Drop one label set; silent (False) when it is not there."""
+        with self._lock:
+            return self._values.pop(tuple(labelvalues), None) is not None
+
     def collect(self) -> Iterable[Metric]:
         # An 'untyped' family keeps both the family name and sample names
         # exactly as configured (prometheus_client would append '_total' to a
@@ -95,6 +105,51 @@ class _ExactNameCounterChild:
         self._parent._inc(self._key, amount)
 
 
+class _TrackedGauge(Gauge):
+    """A Gauge that keeps the label sets it has handed out, so that removing
+    one can say whether it was there — prometheus_client keeps that to
+    itself, and whether ``remove`` raises on an absent label set depends on
+    its version. Label values are positional, as everywhere in this
+    package."""
+
+    def __init__(self, *args: Any, **kwargs: Any):
+        super().__init__(*args, **kwargs)
+        self._label_sets: Set[Tuple[str, ...]] = set()
+        self._label_sets_lock = threading.Lock()
+
+    def labels(self, *labelvalues: Any, **labelkwargs: Any) -> Any:
+        # on the reconciler's hot path (three calls per run): a label set
+        # seen before costs one set lookup, without the lock. A remove()
+        # that slips in between that lookup and the child's re-creation
+        # leaves a child the set does not know; remove() therefore always
+        # removes the child as well, so the next one clears it.
+        if labelvalues in self._label_sets:
+            return super().labels(*labelvalues)
+        if labelkwargs:
+            raise ValueError("label values are given by position here")
+        with self._label_sets_lock:
+            child = super().labels(*labelvalues)
+            self._label_sets.add(tuple(str(v) for v in labelvalues))
+        return child
+
+    def remove(self, *labelvalues: Any) -> bool:  # type: ignore[override]
+        """Drop one label set; silent when it is not there. True when it
+        was (exact unless the same label set is being written meanwhile)."""
+        key = tuple(str(v) for v in labelvalues)
+        with self._label_sets_lock:
+            known = key in self._label_sets
+            self._label_sets.discard(key)
+            try:
+                super().remove(*key)
+            except KeyError:
+                pass
+        return known
+
+    def label_sets(self) -> int:
+        with self._label_sets_lock:
+            return len(self._label_sets)
+
+
 _LABELS = (HC_NAME_LABEL, WF_LABEL)
 
 MonitorSuccess = _ExactNameCounter(
@@ -103,19 +158,19 @@ MonitorSuccess = _ExactNameCounter(
 MonitorError = _ExactNameCounter(
     "healthcheck_error_count", "The total number of errored healthcheck resources", _LABELS
 )
-MonitorRuntime = Gauge(
+MonitorRuntime = _TrackedGauge(
     "healthcheck_runtime_seconds",
     "Time taken for the workflow to complete.",
     _LABELS,
     registry=REGISTRY,
 )
-MonitorStartedTime = Gauge(
+MonitorStartedTime = _TrackedGauge(
     "healthcheck_starttime",
     "Time taken for the workflow to complete.",
     _LABELS,
     registry=REGISTRY,
 )
-MonitorFinishedTime = Gauge(
+MonitorFinishedTime = _TrackedGauge(
     "healthcheck_finishedtime",
     "Time taken for the workflow to complete.",
     _LABELS,
@@ -127,8 +182,11 @@ REGISTRY.register(MonitorError)  # type: ignore[arg-type]
 
 # Dynamic custom-metric gauges, guarded by an RW-ish lock (the reference fixed
 # a data race here with an RWMutex — collector.go:50-51,92-109, issue #288).
-custom_gauge_metrics: Dict[str, Gauge] = {}
+custom_gauge_metrics: Dict[str, _TrackedGauge] = {}
 _custom_lock = threading.Lock()
+# HealthCheck name -> the dynamic gauges it has a child in ("a-b" and "a_b"
+# share their gauges), so that forgetting a name does not walk every gauge
+_custom_owned: Dict[str, Set[str]] = {}
 
 
 def create_dynamic_prometheus_metric(
@@ -189,15 +247,52 @@ def create_dynamic_prometheus_metric(
                 gauge = custom_gauge_metrics.get(full_name)
                 if gauge is None:
                     try:
-                        gauge = Gauge(full_name, help_text, (HC_NAME_LABEL,), registry=registry)
+                        gauge = _TrackedGauge(full_name, help_text, (HC_NAME_LABEL,),
+                                              registry=registry)
                         custom_gauge_metrics[full_name] = gauge
                     except ValueError as e:
                         log.error("Error registering %s metric %s", full_name, e)
                         continue
                 gauge.labels(name).set(value)
+                _custom_owned.setdefault(name, set()).add(full_name)
             updated.append(full_name)
             log.info("Successfully collected metric for %s, metric: %s=%s", name, full_name, value)
     return updated
+
+
+_STATIC_SERIES = (MonitorSuccess, MonitorError, MonitorRuntime,
+                  MonitorStartedTime, MonitorFinishedTime)
+_WORKFLOW_LABELS = ("healthCheck", "remedy")
+
+
+def forget_healthcheck(name: str, registry: CollectorRegistry = REGISTRY) -> int:
+    """Remove every series of the HealthCheck ``name``: its ``healthCheck``
+    and ``remedy`` label sets of the five static series, and its child of
+    every dynamic gauge. A dynamic gauge left without any child is
+    unregistered from ``registry`` and dropped from ``custom_gauge_metrics``,
+    so a later check of that name registers it afresh, help text included;
+    one that still has another check's child (``a-b`` and ``a_b`` share
+    their gauges) stays. Unknown names are not an error. Returns the number
+    of label sets removed."""
+    removed = 0
+    for series in _STATIC_SERIES:
+        for wf_label in _WORKFLOW_LABELS:
+            if series.remove(name, wf_label):
+                removed += 1
+    with _custom_lock:
+        for full_name in _custom_owned.pop(name, ()):
+            gauge = custom_gauge_metrics.get(full_name)
+            if gauge is None:
+                continue
+            if gauge.remove(name):
+                removed += 1
+            if gauge.label_sets() == 0:
+                del custom_gauge_metrics[full_name]
+                try:
+                    registry.unregister(gauge)
+                except KeyError:
+                    pass  # registered with another registry than this one
+    return removed
 
 
 def exposition(registry: CollectorRegistry = REGISTRY) -> bytes:
