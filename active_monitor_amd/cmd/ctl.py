@@ -10,8 +10,11 @@ framework's standalone ``--serve-api`` endpoint:
     amctl --server ... apply -f examples/inline-hello.yaml
     amctl --server ... delete hc inline-hello -n health
     amctl --server ... logs hc inline-hello -n health
+    amctl --server ... run hc inline-hello -n health --wait
 
-``logs`` needs the standalone apiserver: on a cluster the output of a
+``run`` asks the controller to run a check now (docs/OPERATIONS.md, "Running
+a check on demand"); it is ``kubectl annotate --overwrite`` with a fresh
+token, plus the waiting. ``logs`` and ``run --logs`` need the standalone apiserver: on a cluster the output of a
 workflow is the logs of its pods (``kubectl logs``, ``argo logs``).
 """
 from __future__ import annotations
@@ -19,12 +22,19 @@ from __future__ import annotations
 import argparse
 import asyncio
 import sys
+import time
 from datetime import datetime, timezone
 from typing import Any, Dict, List, Optional
 
 import yaml
 
 from .. import API_VERSION
+from ..api.runrequest import (
+    RUN_HANDLED_ANNOTATION,
+    RUN_REQUESTED_ANNOTATION,
+    RUN_WORKFLOW_ANNOTATION,
+    new_run_token,
+)
 from ..api.types import parse_k8s_time
 from ..kube.config import get_config
 from ..kube.errors import (
@@ -240,6 +250,124 @@ async def cmd_logs(client: HttpClient, args) -> int:
     return 0
 
 
+class _RunTimeout(Exception):
+    """``amctl run --wait`` ran out of time; the message names the stage."""
+
+
+_RUN_POLL_SECS = 0.1
+_TERMINAL = ("Succeeded", "Failed")
+
+
+async def _run_handled(client: HttpClient, namespace: str, name: str,
+                       token: str, deadline: float) -> Dict[str, Any]:
+    """Wait until the controller has acknowledged ``token``; the HealthCheck
+    as it stood then."""
+    while True:
+        hc = await client.get(API_VERSION, "HealthCheck", namespace, name)
+        annotations = hc["metadata"].get("annotations") or {}
+        if annotations.get(RUN_HANDLED_ANNOTATION) == token:
+            return hc
+        if time.monotonic() >= deadline:
+            raise _RunTimeout("no controller handled the request: is one "
+                              "running, and does it own this check?")
+        await asyncio.sleep(_RUN_POLL_SECS)
+
+
+async def _run_verdict(client: HttpClient, namespace: str, name: str,
+                       wf_namespace: str, wf_name: str, deadline: float) -> str:
+    """Wait until the Workflow that served the request is Succeeded or
+    Failed. One that is gone already (TTL) has left its verdict in the
+    HealthCheck's status."""
+    while True:
+        try:
+            wf = await client.get(WF_API_VERSION, "Workflow", wf_namespace, wf_name)
+            phase = (wf.get("status") or {}).get("phase")
+        except NotFoundError:
+            hc = await client.get(API_VERSION, "HealthCheck", namespace, name)
+            status = hc.get("status") or {}
+            phase = None
+            if status.get("lastSuccessfulWorkflow") == wf_name:
+                phase = "Succeeded"
+            elif status.get("lastFailedWorkflow") == wf_name:
+                phase = "Failed"
+        if phase in _TERMINAL:
+            return phase
+        if time.monotonic() >= deadline:
+            raise _RunTimeout(f"workflow {wf_name} is still running")
+        await asyncio.sleep(_RUN_POLL_SECS)
+
+
+async def _run_follow_logs(client: HttpClient, wf_namespace: str, wf_name: str,
+                           deadline: float) -> None:
+    async def follow() -> None:
+        out = sys.stdout.buffer
+        async for chunk in client.logs(wf_namespace, wf_name, follow=True, prefix=True):
+            out.write(chunk)
+            out.flush()
+
+    try:
+        await asyncio.wait_for(follow(), max(0.0, deadline - time.monotonic()))
+    except asyncio.TimeoutError:
+        raise _RunTimeout(f"workflow {wf_name} is still running")
+    except NotFoundError as e:
+        raise _LogsError(
+            f"{e.message} (workflow {wf_name}: a workflow and its logs "
+            "are deleted together once the engine TTL has passed)")
+
+
+async def cmd_run(client: HttpClient, args) -> int:
+    wait = args.wait or args.logs
+    if args.all and args.names:
+        print("error: --all takes every healthcheck of the namespace: give "
+              "no names with it", file=sys.stderr)
+        return 2
+    if not args.all and not args.names:
+        print("error: name a healthcheck, or give --all", file=sys.stderr)
+        return 2
+    if args.logs and (args.all or len(args.names) != 1):
+        print("error: --logs follows one run: give a single name", file=sys.stderr)
+        return 2
+    names = list(args.names)
+    if args.all:
+        names = [o["metadata"]["name"] for o in
+                 await client.list(API_VERSION, "HealthCheck", args.namespace)]
+    requested = []
+    for name in names:
+        token = new_run_token()
+        await client.patch(
+            API_VERSION, "HealthCheck", args.namespace, name,
+            {"metadata": {"annotations": {RUN_REQUESTED_ANNOTATION: token}}})
+        print(f"healthcheck/{name} run requested ({token})", flush=True)
+        requested.append((name, token))
+    if not wait:
+        return 0
+    deadline = time.monotonic() + args.timeout
+    rc = 0
+    for name, token in requested:
+        try:
+            hc = await _run_handled(client, args.namespace, name, token, deadline)
+            wf_name = hc["metadata"]["annotations"].get(RUN_WORKFLOW_ANNOTATION, "")
+            resource = ((hc.get("spec") or {}).get("workflow") or {}).get("resource") or {}
+            wf_namespace = resource.get("namespace") or args.namespace
+            print(f"healthcheck/{name} running as workflow {wf_name}", flush=True)
+            if args.logs:
+                await _run_follow_logs(client, wf_namespace, wf_name, deadline)
+            phase = await _run_verdict(client, args.namespace, name,
+                                       wf_namespace, wf_name, deadline)
+        except _RunTimeout as e:
+            print(f"error: healthcheck/{name}: {e}", file=sys.stderr)
+            rc = 2
+            continue
+        except _LogsError as e:
+            print(f"Error: {e}", file=sys.stderr)
+            rc = max(rc, 1)
+            continue
+        print(f"healthcheck/{name} {phase} (workflow {wf_name})", flush=True)
+        if phase != "Succeeded":
+            rc = max(rc, 1)
+    return rc
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="amctl", description=__doc__.splitlines()[0])
     p.add_argument("--server", required=True, help="apiserver URL")
@@ -293,6 +421,23 @@ def build_parser() -> argparse.ArgumentParser:
                        help="hc: the last successful workflow")
     lg.add_argument("--no-prefix", action="store_true",
                     help="do not put the node's display name before each line")
+
+    rn = sub.add_parser(
+        "run", help="ask the controller to run healthchecks now")
+    rn.add_argument("resource", choices=sorted(
+        a for a, (_, kind) in ALIASES.items() if kind == "HealthCheck"))
+    rn.add_argument("names", nargs="*", metavar="NAME")
+    rn.add_argument("-n", "--namespace", default="health")
+    rn.add_argument("--all", action="store_true",
+                    help="every healthcheck of the namespace")
+    rn.add_argument("--wait", action="store_true",
+                    help="wait for the run: exit 0 when all succeeded, 1 when "
+                         "any failed, 2 when --timeout passed")
+    rn.add_argument("--timeout", type=float, default=300.0, metavar="SECS",
+                    help="how long --wait waits, in all (default: 300)")
+    rn.add_argument("--logs", action="store_true",
+                    help="follow the run's output (implies --wait; one name; "
+                         "standalone apiserver)")
     return p
 
 
@@ -306,7 +451,7 @@ async def run(args) -> int:
     try:
         handler = {"get": cmd_get, "describe": cmd_describe,
                    "apply": cmd_apply, "delete": cmd_delete,
-                   "logs": cmd_logs}[args.command]
+                   "logs": cmd_logs, "run": cmd_run}[args.command]
         return await handler(client, args)
     except NotFoundError as e:
         print(f"Error: {e}", file=sys.stderr)

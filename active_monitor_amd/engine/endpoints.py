@@ -156,6 +156,7 @@ async def _handle(reader: asyncio.StreamReader, writer: asyncio.StreamWriter,
                     "queue_depth": len(getattr(manager, "queue", [])),
                     "reconciles": getattr(rec, "reconcile_count", 0),
                     "completed_runs": getattr(rec, "completed_runs", 0),
+                    "on_demand_runs": getattr(rec, "on_demand_runs", 0),
                     "active_watches": rec.active_watches() if rec else 0,
                     "armed_timers": len(getattr(rec, "repeat_timers_by_name", {})),
                     "cron_time_zone": getattr(rec, "cron_time_zone", None),

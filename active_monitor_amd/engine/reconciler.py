@@ -33,6 +33,12 @@ from dataclasses import dataclass
 from typing import Any, Awaitable, Dict, Optional, Set, Tuple
 
 from .. import API_VERSION
+from ..api.runrequest import (
+    RUN_HANDLED_ANNOTATION,
+    RUN_REQUEST_ANNOTATION,
+    RUN_WORKFLOW_ANNOTATION,
+    pending_run_request,
+)
 from ..api.types import HealthCheck, k8s_now, parse_k8s_time
 from ..kube.client import EventRecorder, KubeClient
 from ..kube.errors import ConflictError, NotFoundError, is_storage_error
@@ -130,9 +136,19 @@ class HealthCheckReconciler:
         # name -> namespaces whose check of that name has emitted metrics;
         # the series carry the name alone, so they go with the last of them
         self._metric_namespaces: Dict[str, Set[str]] = {}
+        # run requests (api/runrequest.py). A submitted run whose
+        # acknowledgement is not written yet: key -> (token, workflow name,
+        # uid), so that a failed ack write is retried without resubmitting
+        self._run_acks: Dict[Tuple[str, str], Tuple[str, str, str]] = {}
+        # keys whose reconcile was put off because a run was in flight; they
+        # are queued again when the last watch task of the key is done
+        self._rerun_after_watch: Set[Tuple[str, str]] = set()
+        # paused (manual-only) checks with an on-demand run in flight
+        self._manual_runs: Set[Tuple[str, str]] = set()
         # observability for benchmarks/tests
         self.reconcile_count = 0
         self.completed_runs = 0
+        self.on_demand_runs = 0
 
     # ------------------------------------------------------------------
     # timers
@@ -190,6 +206,13 @@ class HealthCheckReconciler:
                 tasks.discard(t)
                 if not tasks:
                     self._watch_tasks.pop(key, None)
+            if (self._rerun_after_watch or self._manual_runs) and not self._watch_tasks.get(key):
+                self._manual_runs.discard(key)
+                if key in self._rerun_after_watch:
+                    # a reconcile the in-flight guard put off: only now, with
+                    # the task gone from the registry, can it get past it
+                    self._rerun_after_watch.discard(key)
+                    self.queue.add_nowait(key)
             if not t.cancelled() and t.exception() is not None:
                 log.error("watch task for %s failed: %s", key, t.exception())
 
@@ -204,7 +227,11 @@ class HealthCheckReconciler:
         """Stop driving a key: its repeat timer is stopped and its in-flight
         watches are cancelled. True when there was a timer to stop."""
         stopped = self._stop_timer(name, namespace)
-        self._cancel_watches((namespace, name))
+        key = (namespace, name)
+        self._run_acks.pop(key, None)
+        self._rerun_after_watch.discard(key)
+        self._manual_runs.discard(key)
+        self._cancel_watches(key)
         return stopped
 
     def active_watches(self) -> int:
@@ -349,13 +376,31 @@ class HealthCheckReconciler:
         if spec.workflow.resource is None:
             return ReconcileResult()
         wf_namespace = spec.workflow.resource.namespace
+        key = (hc.namespace, hc.name)
+        # the one lookup a check nobody asks to run pays for run requests
+        run_token = pending_run_request(hc.metadata) if hc.metadata.annotations else None
+        unacked = self._run_acks.get(key) if self._run_acks else None
+        if unacked is not None:
+            if unacked[0] == run_token and unacked[2] == hc.metadata.uid:
+                # the run is submitted and only its acknowledgement failed:
+                # repeat the write, not the run
+                await self._ack_run_request(key)
+                return ReconcileResult()
+            del self._run_acks[key]  # withdrawn, replaced, or another object
 
         finished_unix = 0.0
         t = parse_k8s_time(hc.status.finished_at)
         if t is not None:
             finished_unix = t.timestamp()
 
-        if spec.repeat_after_sec <= 0 and spec.schedule.cron == "":
+        paused = spec.repeat_after_sec <= 0 and spec.schedule.cron == ""
+        if paused and run_token is None:
+            if key in self._manual_runs:
+                # an on-demand run of this paused check is in flight: a
+                # Stopped written from what this reconcile read could land
+                # after the run's result and take its counts back
+                self._rerun_after_watch.add(key)
+                return ReconcileResult()
             # pause branch (:238-250) — exact status strings
             hc.status.status = "Stopped"
             hc.status.error_message = (
@@ -372,14 +417,21 @@ class HealthCheckReconciler:
             )
             await self.update_healthcheck_status(hc)
             return ReconcileResult()
-        if not from_timer and self._watch_tasks.get((hc.namespace, hc.name)):
+        if self._watch_tasks.get(key) and (
+            not from_timer or key not in self.repeat_timers_by_name
+        ):
             # a run for this CR is already in flight: spurious reconciles
             # (informer list/watch overlap at startup, spec edits mid-run)
             # must not submit a duplicate workflow. The reference double-
             # submits here and parks a second blocked goroutine per duplicate
-            # (SURVEY.md §2.3.1); the clean rebuild closes that hole.
+            # (SURVEY.md §2.3.1); the clean rebuild closes that hole. A timer
+            # tick whose timer is gone is the tick an on-demand run replaced.
+            if run_token is not None:
+                # the run in flight started before the request and does not
+                # serve it: the request is served when that run is done
+                self._rerun_after_watch.add(key)
             return ReconcileResult()
-        if spec.repeat_after_sec <= 0:
+        if spec.repeat_after_sec <= 0 and not paused:
             # cron branch (:251-263): +1s compensates integer truncation
             try:
                 spec.repeat_after_sec = seconds_until_next(
@@ -397,10 +449,19 @@ class HealthCheckReconciler:
         # computed interval
         if (
             not from_timer
+            and run_token is None
             and int(time.time() - finished_unix) < spec.repeat_after_sec
             and self.get_timer_by_name(hc.name, hc.namespace) is not None
         ):
             return ReconcileResult()
+
+        if run_token is not None:
+            # never two runs at once: the run that serves the request takes
+            # the place of the pending tick, and its completion arms the
+            # timer again by the usual rule
+            self._stop_timer(hc.name, hc.namespace)
+            self.on_demand_runs += 1
+            await self._event(hc, "Normal", "Workflow run requested on demand")
 
         try:
             await self.rbac.create_rbac_for_workflow(hc, HEALTHCHECK)
@@ -408,14 +469,46 @@ class HealthCheckReconciler:
             await self._event(hc, "Warning", "Error creating RBAC for HealthCheckWorkflow")
             raise
 
-        generated_name = await self.create_submit_workflow(hc)
-        self._driven_uid[(hc.namespace, hc.name)] = hc.metadata.uid
+        generated_name = await self.create_submit_workflow(hc, run_token)
+        self._driven_uid[key] = hc.metadata.uid
+        if run_token is not None and paused:
+            self._manual_runs.add(key)
         # non-blocking watch: the reconcile worker is freed immediately
         self._spawn_watch(
-            (hc.namespace, hc.name),
-            self.watch_workflow_reschedule(wf_namespace, generated_name, hc),
+            key,
+            self.watch_workflow_reschedule(
+                wf_namespace, generated_name, hc, on_demand=run_token is not None
+            ),
         )
+        if run_token is not None:
+            self._run_acks[key] = (run_token, generated_name, hc.metadata.uid)
+            await self._ack_run_request(key)
         return ReconcileResult()
+
+    async def _ack_run_request(self, key: Tuple[str, str]) -> None:
+        """Write ``run-handled`` and ``run-workflow`` for the run remembered
+        in ``_run_acks``, in one merge patch. An error leaves the memory in
+        place and propagates: the reconcile is requeued and repeats only
+        this write. The guarantee is at-least-once: a controller that dies
+        between the submit and this write serves the request again."""
+        token, wf_name, uid = self._run_acks[key]
+        namespace, name = key
+        try:
+            out = await self.client.patch(
+                API_VERSION, HC_KIND, namespace, name,
+                {"metadata": {"annotations": {
+                    RUN_HANDLED_ANNOTATION: token,
+                    RUN_WORKFLOW_ANNOTATION: wf_name,
+                }}},
+            )
+        except NotFoundError:
+            self._run_acks.pop(key, None)  # deleted meanwhile: nothing to tell
+            return
+        self._run_acks.pop(key, None)
+        if not uid or ((out.get("metadata") or {}).get("uid") or uid) == uid:
+            # read-your-writes: a cached read from before this write would
+            # show the request as still pending
+            self.note_written(namespace, name, out)
 
     # ------------------------------------------------------------------
     # Submit (reference :502-571)
@@ -443,9 +536,11 @@ class HealthCheckReconciler:
         "Successfully created remedyWorkflow",
     )
 
-    async def _create_submit(self, hc: HealthCheck, remedy: bool) -> str:
+    async def _create_submit(self, hc: HealthCheck, remedy: bool,
+                             run_token: Optional[str] = None) -> str:
         """Parse ``spec.workflow`` (or ``spec.remedyworkflow``) and create the
-        Workflow; returns its generated name."""
+        Workflow; returns its generated name. ``run_token`` marks the check
+        Workflow that serves a run request."""
         wf_spec = hc.spec.remedy_workflow if remedy else hc.spec.workflow
         if remedy and wf_spec.resource is None:
             raise ValueError("RemedyWorkflow Resource is nil")
@@ -469,12 +564,16 @@ class HealthCheckReconciler:
             },
             "spec": spec,
         }
+        if run_token is not None:
+            wf["metadata"]["annotations"] = {RUN_REQUEST_ANNOTATION: run_token}
         created = await self.client.create(wf, transfer=True)
         await self._event(hc, "Normal", created_ok)
         return created["metadata"]["name"]
 
-    def create_submit_workflow(self, hc: HealthCheck) -> Awaitable[str]:
-        return self._create_submit(hc, remedy=False)
+    def create_submit_workflow(
+        self, hc: HealthCheck, run_token: Optional[str] = None
+    ) -> Awaitable[str]:
+        return self._create_submit(hc, remedy=False, run_token=run_token)
 
     def create_submit_remedy_workflow(self, hc: HealthCheck) -> Awaitable[str]:
         return self._create_submit(hc, remedy=True)
@@ -597,7 +696,8 @@ class HealthCheckReconciler:
         return status
 
     async def watch_workflow_reschedule(
-        self, wf_namespace: str, wf_name: str, hc: HealthCheck
+        self, wf_namespace: str, wf_name: str, hc: HealthCheck,
+        on_demand: bool = False,
     ) -> None:
         then = k8s_now()
         then_unix = time.time()
@@ -619,6 +719,15 @@ class HealthCheckReconciler:
                 "indicate that either the healthcheck was removed or the Workflow "
                 "was GC'd before active-monitor could obtain the status",
             )
+            if on_demand and repeat_after_sec > 0:
+                # the run took the pending tick's place (its timer was
+                # stopped): without a result to re-arm from, the schedule
+                # is put back here, so the check is never left unscheduled
+                fresh = await self._get_live_hc(hc)
+                if fresh is not None:
+                    self._arm_repeat_timer(
+                        hc.name, hc.namespace,
+                        self._next_delay(fresh, repeat_after_sec))
             return
         await self._apply_check_result(hc, wf_name, status, then, then_unix)
         try:
@@ -770,18 +879,12 @@ class HealthCheckReconciler:
         fresh = await self._get_live_hc(hc)
         if fresh is None:
             return
-        # cron CRs: recompute the delay at completion time so the next run
-        # lands on the cron tick, not submit-time + interval (the reference
-        # re-arms with the stale submit-time value, drifting by the run's
-        # duration — :746-752)
-        fresh_spec = fresh.get("spec") or {}
-        cron = ((fresh_spec.get("schedule") or {}).get("cron")) or ""
-        if int(fresh_spec.get("repeatAfterSec", 0) or 0) <= 0 and cron:
-            try:
-                repeat_after_sec = seconds_until_next(cron, default_zone=self._cron_zone)
-            except CronParseError:
-                pass  # keep the submit-time value
-        self._arm_repeat_timer(hc.name, hc.namespace, repeat_after_sec)
+        repeat_after_sec = self._next_delay(fresh, repeat_after_sec)
+        # <= 0: the on-demand run of a paused (manual-only) check, which has
+        # no next run to arm — not even a zero-delay one
+        armed = repeat_after_sec > 0
+        if armed:
+            self._arm_repeat_timer(hc.name, hc.namespace, repeat_after_sec)
         try:
             await self.update_healthcheck_status(hc, fresh=fresh)
         except NotFoundError:
@@ -791,7 +894,22 @@ class HealthCheckReconciler:
             await self._event(hc, "Warning", "Error updating healthcheck resource")
             self._stop_timer(hc.name, hc.namespace)
             raise
-        await self._event(hc, "Normal", "Rescheduled workflow for next run")
+        if armed:
+            await self._event(hc, "Normal", "Rescheduled workflow for next run")
+
+    def _next_delay(self, fresh: Dict[str, Any], repeat_after_sec: float) -> float:
+        """Cron CRs: recompute the delay at completion time so the next run
+        lands on the cron tick, not submit-time + interval (the reference
+        re-arms with the stale submit-time value, drifting by the run's
+        duration — :746-752)."""
+        fresh_spec = fresh.get("spec") or {}
+        cron = ((fresh_spec.get("schedule") or {}).get("cron")) or ""
+        if int(fresh_spec.get("repeatAfterSec", 0) or 0) <= 0 and cron:
+            try:
+                return seconds_until_next(cron, default_zone=self._cron_zone)
+            except CronParseError:
+                pass  # keep the submit-time value
+        return repeat_after_sec
 
     # ------------------------------------------------------------------
     # Remedy (reference :677-721, :759-786)
