@@ -33,7 +33,7 @@ def parse_bind_address(addr: str) -> Optional[Tuple[str, int]]:
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from ..kube.standalone import add_log_flags
+    from ..kube.standalone import add_limit_flags, add_log_flags
 
     p = argparse.ArgumentParser(
         prog="active-monitor-amd",
@@ -96,6 +96,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "(default, or 'Local': the controller's own clock; "
                         "also: AM_CRON_TIME_ZONE in the environment)")
     add_log_flags(p)
+    add_limit_flags(p, "workflow")
     p.add_argument("--shard-index", type=int, default=0,
                    help="this controller's shard (keyspace split by CR-name hash)")
     p.add_argument("--shard-count", type=int, default=1,
@@ -130,7 +131,13 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         gc.set_threshold(args.gc_threshold, 50, 50)
     # looked up when called, not at import: tests substitute the Manager
     from ..engine import Manager
-    from ..kube.standalone import build_engine, open_logs, open_store, stop_on_signals
+    from ..kube.standalone import (
+        build_engine,
+        limit_options,
+        open_logs,
+        open_store,
+        stop_on_signals,
+    )
 
     level = {"debug": logging.DEBUG, "info": logging.INFO,
              "warn": logging.WARNING, "error": logging.ERROR}.get(
@@ -174,7 +181,8 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         client = MemoryClient(store)
         logs = open_logs(args, args.workflow_engine, store, log.info)
         engine = build_engine(args.workflow_engine, client, args.data_dir,
-                              logs=logs, namespace=args.namespace)
+                              logs=logs, namespace=args.namespace,
+                              **limit_options(args, "workflow"))
         if args.serve_api:
             from ..kube.server import ApiServerFrontend
 
@@ -210,6 +218,8 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
         metrics_security=metrics_security,
         cron_time_zone=args.cron_time_zone,
     )
+    if engine is not None:
+        manager.workflow_engine = engine  # /statusz shows its stats()
 
     stop = stop_on_signals(stop_event if stop_event is not None else asyncio.Event())
     if engine is not None:
@@ -249,7 +259,7 @@ async def run(args, stop_event: Optional[asyncio.Event] = None) -> int:
 
 
 def main(argv=None) -> int:
-    from ..kube.standalone import check_log_flags
+    from ..kube.standalone import LIMIT_FLAGS, check_limit_flags, check_log_flags
 
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -263,6 +273,10 @@ def main(argv=None) -> int:
         if given and args.backend != "memory":
             parser.error(f"{flag} applies to --backend memory only")
     check_log_flags(parser, args)
+    for option, suffix in LIMIT_FLAGS:
+        if getattr(args, f"workflow_{option}") is not None and args.backend != "memory":
+            parser.error(f"--workflow-{suffix} applies to --backend memory only")
+    check_limit_flags(parser, args, "workflow")
     if args.cron_time_zone:
         from ..engine.cronx import CronParseError, load_zone
 

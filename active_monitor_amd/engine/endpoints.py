@@ -169,6 +169,10 @@ async def _handle(reader: asyncio.StreamReader, writer: asyncio.StreamWriter,
                     "watch_relists": getattr(sub, "relists", 0),
                     "watch_synthetic_deletes": getattr(sub, "synthetic_deletes", 0),
                 }
+                # the standalone process's workflow engine, when it has one
+                wf_engine = getattr(manager, "workflow_engine", None)
+                if wf_engine is not None:
+                    stats["workflow_engine"] = wf_engine.stats()
             body, ctype, code = json.dumps(stats).encode(), "application/json", 200
         elif path.startswith("/healthz"):
             body, ctype, code = b"ok", "text/plain", 200

@@ -86,8 +86,10 @@ def parse_args(argv=None):
                         "and pruning them by the CRD schema (also: "
                         "AM_SCHEMA_VALIDATION=0 in the environment)")
     add_log_flags(p)
+    add_limit_flags(p, "engine")
     args = p.parse_args(argv)
     check_log_flags(p, args)
+    check_limit_flags(p, args, "engine")
     return args
 
 
@@ -110,6 +112,42 @@ def check_log_flags(p: argparse.ArgumentParser, args) -> None:
                         ("--log-max-total-bytes", args.log_max_total_bytes)):
         if value is not None and value < 2:
             p.error(f"{flag} must be 2 or more")
+
+
+#: engine option -> flag suffix, for ``--engine-*`` here and ``--workflow-*``
+#: on the controller
+LIMIT_FLAGS = (("parallelism", "parallelism"),
+               ("namespace_parallelism", "namespace-parallelism"),
+               ("max_processes", "max-processes"))
+
+
+def add_limit_flags(p: argparse.ArgumentParser, prefix: str) -> None:
+    """The flags that bound what the workflow engine runs at once, as
+    ``--<prefix>-parallelism`` and so on, for both entry points."""
+    for (_, suffix), text in zip(LIMIT_FLAGS, (
+            "run at most N workflows at once; the rest wait Pending, "
+            "higher spec.priority first, then older first",
+            "run at most N workflows of one namespace at once",
+            "local engine: at most N workflow processes alive at once, "
+            "over all workflows")):
+        p.add_argument(f"--{prefix}-{suffix}", type=int, default=None, metavar="N",
+                       help=f"{text} (default: unlimited)")
+
+
+def limit_options(args, prefix: str) -> dict:
+    """The limits that were given, as options for :func:`build_engine`."""
+    given = {}
+    for option, suffix in LIMIT_FLAGS:
+        value = getattr(args, f"{prefix}_{suffix}".replace("-", "_"))
+        if value is not None:
+            given[option] = value
+    return given
+
+
+def check_limit_flags(p: argparse.ArgumentParser, args, prefix: str) -> None:
+    for option, value in limit_options(args, prefix).items():
+        if value < 1:
+            p.error(f"--{prefix}-{option.replace('_', '-')} must be a positive integer")
 
 
 def open_logs(args, engine_kind: str, server, info=None):
@@ -237,7 +275,7 @@ async def amain(args) -> int:
                                  accepted_tokens=accepted, logs=logs)
     await frontend.start()
 
-    options = {"ttl_seconds": args.engine_ttl}
+    options = {"ttl_seconds": args.engine_ttl, **limit_options(args, "engine")}
     if args.engine == "scripted-bench":
         options.update(policy=bench_policy(args.remedy_frac), delay=args.engine_delay)
     engine = build_engine(args.engine, MemoryClient(server), args.data_dir,

@@ -1,5 +1,7 @@
 """Workflow execution backends (Argo-CR driven, scripted fake, local executor)."""
 from .engines import (
+    POSTPONED_MESSAGE,
+    QUEUE_EXPIRED_MESSAGE,
     LocalWorkflowEngine,
     ScriptedWorkflowEngine,
     always_fail,
@@ -10,6 +12,8 @@ from .logs import LogStore
 from .validate import validate_workflow_spec
 
 __all__ = [
+    "POSTPONED_MESSAGE",
+    "QUEUE_EXPIRED_MESSAGE",
     "LocalWorkflowEngine",
     "LogStore",
     "ScriptedWorkflowEngine",

@@ -22,6 +22,7 @@ that role in-process:
 from __future__ import annotations
 
 import asyncio
+import bisect
 import logging
 import time
 from typing import Any, Callable, Dict, List, Optional, Tuple
@@ -32,7 +33,13 @@ from ..kube.registry import WF_API_VERSION, WF_KIND
 
 log = logging.getLogger("active_monitor_amd.workflow")
 
-Phase = str  # "Running" | "Succeeded" | "Failed"
+Phase = str  # "Pending" | "Running" | "Succeeded" | "Failed"
+
+#: status.message of a Workflow that waits for one of the engine's slots
+POSTPONED_MESSAGE = ("Workflow processing has been postponed because too many "
+                     "workflows are already running")
+#: status.message of a Workflow whose activeDeadlineSeconds ran out in the queue
+QUEUE_EXPIRED_MESSAGE = "deadline exceeded while waiting to start"
 
 PolicyResult = Optional[Tuple[Phase, str]]
 Policy = Callable[[Dict[str, Any]], PolicyResult]
@@ -50,6 +57,53 @@ def never_complete(wf: Dict[str, Any]) -> PolicyResult:
     return None
 
 
+def _positive(name: str, value: Any) -> Optional[int]:
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError(f"{name} must be a positive integer, got {value!r}")
+    return value
+
+
+def mutex_names(spec: Any) -> List[str]:
+    """Names under ``spec.synchronization.mutex`` and ``.mutexes``, duplicates
+    removed, order kept."""
+    sync = spec.get("synchronization") if isinstance(spec, dict) else None
+    if not isinstance(sync, dict):
+        return []
+    several = sync.get("mutexes")
+    found = [sync.get("mutex")] + (several if isinstance(several, list) else [])
+    return list(dict.fromkeys(
+        str(m["name"]) for m in found if isinstance(m, dict) and m.get("name")
+    ))
+
+
+def _priority(spec: Dict[str, Any]) -> int:
+    try:
+        return int(spec.get("priority") or 0)
+    except (TypeError, ValueError):
+        return 0
+
+
+class _Queued:
+    """A Workflow that waits to be admitted. ``order`` sorts the queue:
+    higher ``spec.priority``, then earlier ``creationTimestamp``, then
+    arrival. ``postponed`` is the task of its one ``Pending`` write, which
+    the next write to the same Workflow waits for."""
+
+    __slots__ = ("wf", "key", "ns", "order", "mutexes", "postponed", "expiry")
+
+    def __init__(self, wf: Dict[str, Any], key: str, ns: str, order: Tuple[int, str, int],
+                 mutexes: List[Tuple[str, str]]):
+        self.wf = wf
+        self.key = key
+        self.ns = ns
+        self.order = order
+        self.mutexes = mutexes
+        self.postponed: Optional["asyncio.Future[Any]"] = None
+        self.expiry: Optional[asyncio.TimerHandle] = None
+
+
 class _EngineBase:
     """``ttl_seconds`` deletes completed workflows after the given delay —
     the role Argo's ``ttlStrategy.secondsAfterCompletion`` plays for the
@@ -61,18 +115,44 @@ class _EngineBase:
     there. One that was never picked up runs as if just added; one left
     ``Running`` by a previous process is failed, never re-run (a remedy is
     not idempotent and a half-run DAG cannot be resumed); one already
-    terminal gets its lost TTL timer re-armed for the time it has left."""
+    terminal gets its lost TTL timer re-armed for the time it has left; one
+    found ``Pending`` (queued by a previous process) is admitted anew.
+
+    ``parallelism`` and ``namespace_parallelism`` bound how many Workflows
+    run at once, in all and per namespace — the Argo controller's settings of
+    the same names; ``max_processes`` is for the engine that starts
+    processes. None is unlimited. A Workflow that names mutexes
+    (``spec.synchronization``) runs only while it holds all of them, limits
+    or not. One that cannot start waits ``Pending`` in a queue ordered by
+    priority, then age; docs/OPERATIONS.md, "Bounding what runs at once"."""
 
     DEFAULT_TTL = 1800.0
     INTERRUPTED_MESSAGE = "workflow interrupted: engine restarted"
 
     def __init__(self, client: KubeClient, namespace: Optional[str] = None,
                  ttl_seconds: Optional[float] = DEFAULT_TTL,
-                 recover: bool = False):
+                 recover: bool = False, parallelism: Optional[int] = None,
+                 namespace_parallelism: Optional[int] = None,
+                 max_processes: Optional[int] = None):
         self.client = client
         self.namespace = namespace
         self.ttl_seconds = ttl_seconds
         self.recover = recover
+        self.parallelism = _positive("parallelism", parallelism)
+        self.namespace_parallelism = _positive("namespace_parallelism",
+                                               namespace_parallelism)
+        self.max_processes = _positive("max_processes", max_processes)
+        # without a Workflow limit only a Workflow that names a mutex is queued
+        self._limited = parallelism is not None or namespace_parallelism is not None
+        self._queue: List[_Queued] = []  # sorted by .order
+        self._queued: Dict[str, _Queued] = {}
+        self._arrivals = 0
+        self._admitted = 0
+        self._admitted_ns: Dict[str, int] = {}
+        self._locked: set = set()  # (namespace, mutex name) of admitted runs
+        self._stopping = False
+        self.postponed_total = 0
+        self.expired_in_queue = 0
         # uids taken from the start-up list; their ADDED event, should the
         # watch deliver one as well, is dropped. Emptied by the first event
         # newer than everything in that list (_recovered_rv).
@@ -97,9 +177,22 @@ class _EngineBase:
             finished.sort(key=lambda pair: pair[0])
             for left, wf in finished:
                 self._schedule_ttl(wf, left)
+            if self._queue:
+                # everything the list held is in the queue: admit in order
+                self._pump()
+                for entry in list(self._queue):
+                    self._postpone(entry)
+        log.info("workflow engine limits: parallelism=%s namespace_parallelism=%s "
+                 "max_processes=%s", *(
+                     "unlimited" if v is None else v for v in self.limits().values()))
         self._task = asyncio.ensure_future(self._loop())
 
     async def stop(self) -> None:
+        # what is queued stays Pending, for a restart over the same store
+        self._stopping = True
+        for entry in self._queue:
+            if entry.expiry is not None:
+                entry.expiry.cancel()
         if self._sub is not None:
             self._sub.close()
         if self._task is not None:
@@ -120,12 +213,14 @@ class _EngineBase:
             if self._recovered and self._taken_at_start(ev["type"], wf):
                 continue
             if ev["type"] == "DELETED":
+                if self._queued:
+                    self._dequeue(wf)
                 self._deleted(wf)
             if ev["type"] != "ADDED":
                 continue
             if (wf.get("status") or {}).get("phase") in ("Succeeded", "Failed"):
                 continue
-            self._spawn(wf, self._run(wf))
+            self._submit(wf)
 
     def _taken_at_start(self, ev_type: str, wf: Dict[str, Any]) -> bool:
         """True for the ADDED event of a workflow that the start-up list
@@ -144,11 +239,159 @@ class _EngineBase:
     def _deleted(self, wf: Dict[str, Any]) -> None:
         """The Workflow is gone: TTL, owner cascade or a user's delete."""
 
-    def _spawn(self, wf: Dict[str, Any], coro: Any) -> None:
-        key = f'{(wf["metadata"].get("namespace", ""))}/{wf["metadata"]["name"]}'
+    def _spawn(self, wf: Dict[str, Any], coro: Any, prefix: str = "") -> "asyncio.Future[Any]":
+        """``prefix`` keeps a side task (``pending:``, ``expired:``) apart
+        from the run of the same Workflow."""
+        key = f'{prefix}{(wf["metadata"].get("namespace", ""))}/{wf["metadata"]["name"]}'
         task = asyncio.ensure_future(coro)
         self._inflight[key] = task
         task.add_done_callback(lambda t, k=key: self._inflight.pop(k, None))
+        return task
+
+    # -- admission --------------------------------------------------------
+
+    def limits(self) -> Dict[str, Optional[int]]:
+        return {"parallelism": self.parallelism,
+                "namespace_parallelism": self.namespace_parallelism,
+                "max_processes": self.max_processes}
+
+    def stats(self) -> Dict[str, Any]:
+        """Counters for ``/statusz``. ``running`` counts the runs in flight,
+        admitted or never queued; ``processes`` the leaf processes alive."""
+        return {
+            "running": sum(1 for key in self._inflight if ":" not in key),
+            "queued": len(self._queue),
+            "postponed_total": self.postponed_total,
+            "expired_in_queue": self.expired_in_queue,
+            "processes": self._processes(),
+            "limits": self.limits(),
+        }
+
+    def _processes(self) -> int:
+        return 0
+
+    def _submit(self, wf: Dict[str, Any], recovering: bool = False) -> None:
+        """Run ``wf`` now, or queue it when a limit or a mutex may stand in
+        its way. ``recovering``: only queue it, start() admits once all that
+        it found is queued."""
+        spec = wf.get("spec")
+        names = mutex_names(spec) if isinstance(spec, dict) and "synchronization" in spec else None
+        if not self._limited and not names:
+            self._spawn(wf, self._run(wf))
+            return
+        meta = wf["metadata"]
+        ns = meta.get("namespace", "")
+        key = f'{ns}/{meta["name"]}'
+        if key in self._queued:
+            return
+        self._arrivals += 1
+        order = (-_priority(spec if isinstance(spec, dict) else {}),
+                 str(meta.get("creationTimestamp") or ""), self._arrivals)
+        entry = _Queued(wf, key, ns, order, [(ns, n) for n in names or ()])
+        bisect.insort(self._queue, entry, key=lambda e: e.order)
+        self._queued[key] = entry
+        if not recovering:
+            self._pump()
+            if key in self._queued:
+                self._postpone(entry)
+
+    def _blocked_by(self, entry: _Queued) -> Optional[str]:
+        """The ``Pending`` message for what keeps ``entry`` from starting
+        now, None when nothing does."""
+        if self.parallelism is not None and self._admitted >= self.parallelism:
+            return POSTPONED_MESSAGE
+        if (self.namespace_parallelism is not None
+                and self._admitted_ns.get(entry.ns, 0) >= self.namespace_parallelism):
+            return POSTPONED_MESSAGE
+        for ns, name in entry.mutexes:
+            if (ns, name) in self._locked:
+                return f"Waiting for {ns}/Mutex/{name} lock"
+        return None
+
+    def _pump(self) -> None:
+        """Admit, in queue order, every Workflow that can start. One that
+        waits for its namespace or for a mutex is passed over."""
+        if self._stopping:
+            return
+        i = 0
+        while i < len(self._queue):
+            if self.parallelism is not None and self._admitted >= self.parallelism:
+                break
+            entry = self._queue[i]
+            if self._blocked_by(entry) is not None:
+                i += 1
+                continue
+            del self._queue[i]
+            del self._queued[entry.key]
+            if entry.expiry is not None:
+                entry.expiry.cancel()
+            # the slot and the mutexes are taken here, all or none, before
+            # the next entry is looked at
+            self._admitted += 1
+            self._admitted_ns[entry.ns] = self._admitted_ns.get(entry.ns, 0) + 1
+            self._locked.update(entry.mutexes)
+            self._spawn(entry.wf, self._run_admitted(entry))
+
+    async def _run_admitted(self, entry: _Queued) -> None:
+        try:
+            if entry.postponed is not None:
+                await asyncio.wait([entry.postponed])  # Pending lands before Running
+            await self._run(entry.wf)
+        finally:
+            self._admitted -= 1
+            left = self._admitted_ns[entry.ns] - 1
+            if left:
+                self._admitted_ns[entry.ns] = left
+            else:
+                del self._admitted_ns[entry.ns]
+            self._locked.difference_update(entry.mutexes)
+            self._pump()
+
+    def _postpone(self, entry: _Queued) -> None:
+        """``entry`` stays in the queue: write ``Pending`` once and start
+        the clock of its deadline."""
+        self.postponed_total += 1
+        wf = entry.wf
+        if (wf.get("status") or {}).get("phase") != "Pending":  # else: recovered
+            message = self._blocked_by(entry) or POSTPONED_MESSAGE
+            entry.postponed = self._spawn(
+                wf, self._set_status(wf, {"phase": "Pending", "message": message}),
+                "pending:")
+        deadline = (wf.get("spec") or {}).get("activeDeadlineSeconds")
+        try:
+            deadline = float(deadline) if deadline and deadline is not True else 0.0
+        except (TypeError, ValueError):
+            deadline = 0.0
+        if deadline > 0:
+            entry.expiry = asyncio.get_event_loop().call_later(
+                deadline, self._expire, entry)
+
+    def _expire(self, entry: _Queued) -> None:
+        if self._queued.get(entry.key) is not entry:
+            return
+        del self._queued[entry.key]
+        self._queue.remove(entry)
+        self.expired_in_queue += 1
+        log.warning("workflow %s waited out its activeDeadlineSeconds in the "
+                    "queue: failing it", entry.key)
+        self._spawn(entry.wf, self._fail_expired(entry), "expired:")
+
+    async def _fail_expired(self, entry: _Queued) -> None:
+        if entry.postponed is not None:
+            await asyncio.wait([entry.postponed])
+        await self._set_status(entry.wf, {
+            "phase": "Failed", "finishedAt": _now_iso(), "message": QUEUE_EXPIRED_MESSAGE,
+        })
+        self._schedule_ttl(entry.wf)
+
+    def _dequeue(self, wf: Dict[str, Any]) -> None:
+        """A DELETED Workflow leaves the queue; it never runs."""
+        meta = wf["metadata"]
+        entry = self._queued.pop(f'{meta.get("namespace", "")}/{meta["name"]}', None)
+        if entry is not None:
+            self._queue.remove(entry)
+            if entry.expiry is not None:
+                entry.expiry.cancel()
 
     def _recover(self, wf: Dict[str, Any], finished: List[Any]) -> None:
         """Handle one Workflow found at start by the state it is in; a
@@ -164,7 +407,7 @@ class _EngineBase:
             if self.ttl_seconds is not None:
                 finished.append((self._ttl_left(status.get("finishedAt")), wf))
             return
-        if phase and phase != "Running":
+        if phase and phase not in ("Running", "Pending"):
             return  # a phase no local engine writes: not ours to touch
         if meta.get("uid"):
             self._recovered.add(meta["uid"])
@@ -173,9 +416,9 @@ class _EngineBase:
                                          int(meta.get("resourceVersion")))
             except (TypeError, ValueError):
                 pass
-        if not phase:
+        if phase != "Running":
             log.info("recovering pending workflow %s", key)
-            self._spawn(wf, self._run(wf))
+            self._submit(wf, recovering=True)
         else:
             log.warning("workflow %s was running when the engine stopped: "
                         "failing it", key)
@@ -268,8 +511,12 @@ class ScriptedWorkflowEngine(_EngineBase):
         namespace: Optional[str] = None,
         ttl_seconds: Optional[float] = _EngineBase.DEFAULT_TTL,
         recover: bool = False,
+        parallelism: Optional[int] = None,
+        namespace_parallelism: Optional[int] = None,
+        max_processes: Optional[int] = None,  # accepted, starts no processes
     ):
-        super().__init__(client, namespace, ttl_seconds, recover)
+        super().__init__(client, namespace, ttl_seconds, recover, parallelism,
+                         namespace_parallelism, max_processes)
         self.policy = policy
         self.delay = delay
         self.completed = 0
@@ -335,12 +582,23 @@ class LocalWorkflowEngine(_EngineBase):
 
     def __init__(self, client: KubeClient, namespace: Optional[str] = None,
                  ttl_seconds: Optional[float] = _EngineBase.DEFAULT_TTL,
-                 recover: bool = False, logs: Any = None):
-        super().__init__(client, namespace, ttl_seconds, recover)
+                 recover: bool = False, logs: Any = None,
+                 parallelism: Optional[int] = None,
+                 namespace_parallelism: Optional[int] = None,
+                 max_processes: Optional[int] = None):
+        super().__init__(client, namespace, ttl_seconds, recover, parallelism,
+                         namespace_parallelism, max_processes)
+        from .executor import Bound
+
         self.completed = 0
+        #: the leaf processes of all runs; holds at most ``max_processes``
+        self.process_slots = Bound(self.max_processes)
         #: a :class:`~.logs.LogStore` for what the leaves print, or None;
         #: whoever built it closes it
         self.logs = logs
+
+    def _processes(self) -> int:
+        return self.process_slots.held
 
     def _deleted(self, wf: Dict[str, Any]) -> None:
         if self.logs is not None:
@@ -356,7 +614,7 @@ class LocalWorkflowEngine(_EngineBase):
 
     async def _run(self, wf: Dict[str, Any]) -> None:
         from .executor import WorkflowRun
-        from .validate import validate_workflow_spec
+        from .validate import ignored_synchronization, validate_workflow_spec
 
         spec = wf.get("spec") or {}
         meta = wf["metadata"]
@@ -375,7 +633,11 @@ class LocalWorkflowEngine(_EngineBase):
         if problems:
             phase, message = "Failed", problems[0]
         else:
-            run = WorkflowRun(spec, name, ns, logs=logs)
+            ignored = ignored_synchronization(spec)
+            if ignored:
+                log.warning("workflow %s/%s: %s not supported and ignored",
+                            ns, name, " and ".join(ignored))
+            run = WorkflowRun(spec, name, ns, logs=logs, process_slots=self.process_slots)
             try:
                 phase, message, timed_out = await self._run_phases(run, spec)
             except asyncio.CancelledError:

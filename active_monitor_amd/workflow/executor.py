@@ -8,6 +8,7 @@ writes; everything between the two writes happens here.
 from __future__ import annotations
 
 import asyncio
+import collections
 import logging
 import os
 import shutil
@@ -44,6 +45,11 @@ _PIPE_CHUNK = 64 * 1024
 #: after its group was killed a leaf's pipes reach EOF at once, unless a
 #: process that left the group still holds them; it is not waited for longer
 _KILL_DRAIN_SECONDS = 1.0
+#: a killed member of the group that was not the leaf's own child (its parent
+#: exited first) is reaped by whoever adopted it, init as a rule, and stays
+#: in the process table until then; the kill path waits this long for the
+#: group to be empty, so that a workflow reported Failed has left nothing
+_KILL_REAP_SECONDS = 5.0
 
 log = logging.getLogger("active_monitor_amd.workflow")
 
@@ -59,10 +65,67 @@ def _now_iso() -> str:
     return k8s_now()
 
 
+class Bound:
+    """At most ``limit`` holders at a time, served in arrival order; None
+    bounds nothing. ``held`` counts the holders either way. A waiter that is
+    cancelled gives up its place, or the slot it was just handed.
+
+    ``fail_fast`` is set by a DAG that fails fast: its first child to fail
+    sets ``closed`` before it hands its slot on, and a child that gets a
+    slot afterwards does not start."""
+
+    __slots__ = ("limit", "held", "fail_fast", "closed", "_waiters")
+
+    def __init__(self, limit: Optional[int] = None):
+        self.limit = limit
+        self.held = 0
+        self.fail_fast = False
+        self.closed = False
+        self._waiters: "collections.deque[asyncio.Future[None]]" = collections.deque()
+
+    async def acquire(self) -> None:
+        if self.limit is None or (self.held < self.limit and not self._waiters):
+            self.held += 1
+            return
+        fut: "asyncio.Future[None]" = asyncio.get_running_loop().create_future()
+        self._waiters.append(fut)
+        try:
+            await fut
+        except asyncio.CancelledError:
+            if fut.cancelled():
+                try:
+                    self._waiters.remove(fut)
+                except ValueError:
+                    pass  # release() passed it over already
+            else:
+                self.release()  # handed over as the cancellation arrived
+            raise
+
+    def release(self) -> None:
+        self.held -= 1
+        while self._waiters and self.held < self.limit:
+            fut = self._waiters.popleft()
+            if not fut.done():
+                self.held += 1
+                fut.set_result(None)
+
+
+def _parallelism_bound(tmpl: Dict[str, Any]) -> Optional[Bound]:
+    """A new bound for a spec, or for one invocation of a ``steps`` or
+    ``dag`` template, that sets ``parallelism``; None when it does not."""
+    limit = tmpl.get("parallelism")
+    return Bound(limit) if limit is not None else None
+
+
 class WorkflowRun:
     def __init__(self, spec: Dict[str, Any], name: str, namespace: str,
-                 logs: Any = None):
+                 logs: Any = None, process_slots: Optional[Bound] = None):
         self.spec = spec
+        # a leaf process holds one slot of each, taken in this order:
+        # spec.parallelism, then the engine's bound over all of its runs
+        self._process_bounds = [
+            b for b in (_parallelism_bound(spec), process_slots) if b is not None
+        ]
         self.name = name
         self.namespace = namespace
         #: a :class:`~.logs.LogStore`, or None: leaf output is then drained
@@ -282,14 +345,16 @@ class WorkflowRun:
     # -- steps and DAGs ---------------------------------------------------
 
     async def _run_steps(self, tmpl: Dict[str, Any], node_id: str, scope: Scope) -> Tuple[bool, str]:
+        bound = _parallelism_bound(tmpl)
         for i, group in enumerate(tmpl["steps"] or []):
             steps = [s for s in (group if isinstance(group, list) else [group])
                      if isinstance(s, dict)]
             gid = f"{node_id}[{i}]"
             gnode = self._open(gid, f"[{i}]", "StepGroup", None, node_id)
-            results = await _gather(
-                [self._run_call(s, "steps", gid, f"{gid}.{s.get('name')}", scope) for s in steps]
-            )
+            results = await _gather([
+                self._run_call(s, "steps", gid, f"{gid}.{s.get('name')}", scope, bound)
+                for s in steps
+            ])
             failed = [msg for phase, msg, _ in results if phase == "Failed"]
             self._close(gnode, "Failed" if failed else "Succeeded", failed[0] if failed else "")
             if failed:
@@ -301,6 +366,9 @@ class WorkflowRun:
         tasks = {t.get("name"): t for t in dag.get("tasks") or [] if isinstance(t, dict)}
         deps = {name: task_dependencies(t) for name, t in tasks.items()}
         fail_fast = dag.get("failFast", True) is not False
+        bound = _parallelism_bound(tmpl)
+        if bound is not None:
+            bound.fail_fast = fail_fast
         phases: Dict[str, str] = {}
         running: Dict["asyncio.Future[Result]", str] = {}
         first_failure: Optional[str] = None
@@ -322,7 +390,7 @@ class WorkflowRun:
                         omit(name, "omitted: a dependency did not succeed")
                     elif all(s in ("Succeeded", "Skipped") for s in states):
                         fut = asyncio.ensure_future(self._run_call(
-                            tasks[name], "tasks", node_id, f"{node_id}.{name}", scope
+                            tasks[name], "tasks", node_id, f"{node_id}.{name}", scope, bound
                         ))
                         running[fut] = name
                 if not running:
@@ -344,10 +412,12 @@ class WorkflowRun:
         return True, ""
 
     async def _run_call(self, call: Dict[str, Any], kind: str, parent: str, node_id: str,
-                        scope: Scope) -> Result:
+                        scope: Scope, bound: Optional[Bound] = None) -> Result:
         """One step or DAG task: loop expansion, ``when``, arguments, then
         the template it names. Publishes ``steps.NAME.*`` / ``tasks.NAME.*``
-        into the caller's scope when it ran exactly once."""
+        into the caller's scope when it ran exactly once. ``bound`` is the
+        calling template's ``parallelism``: the call, or each item of its
+        loop, holds one slot of it from start to end."""
         name = str(call.get("name"))
         tname = call.get("template")
         try:
@@ -362,13 +432,21 @@ class WorkflowRun:
                     self._run_expanded(
                         call, parent, f"{parent}.{item_display_name(name, i, item)}",
                         item_display_name(name, i, item), {**scope, **item_scope(item)},
+                        bound,
                     )
                     for i, item in enumerate(items)
                 ])
                 failed = [msg for phase, msg, _ in results if phase == "Failed"]
-                scope[f"{kind}.{name}.status"] = "Failed" if failed else "Succeeded"
-                return ("Failed", failed[0], None) if failed else ("Succeeded", "", None)
-            phase, message, outputs = await self._run_expanded(call, parent, node_id, name, scope)
+                if failed:
+                    phase = "Failed"
+                elif any(phase == "Omitted" for phase, _, _ in results):
+                    phase = "Omitted"
+                else:
+                    phase = "Succeeded"
+                scope[f"{kind}.{name}.status"] = phase
+                return phase, failed[0] if failed else "", None
+            phase, message, outputs = await self._run_expanded(
+                call, parent, node_id, name, scope, bound)
         except TemplateError as e:
             self._mark(node_id, name, tname, parent, "Failed", str(e))
             return "Failed", str(e), None
@@ -381,7 +459,24 @@ class WorkflowRun:
         return phase, message, outputs
 
     async def _run_expanded(self, call: Dict[str, Any], parent: str, node_id: str, display: str,
-                            scope: Scope) -> Result:
+                            scope: Scope, bound: Optional[Bound] = None) -> Result:
+        if bound is None:
+            return await self._run_child(call, parent, node_id, display, scope)
+        await bound.acquire()
+        try:
+            if bound.closed:
+                message = "omitted: the DAG failed before this task could start"
+                self._mark(node_id, display, call.get("template"), parent, "Omitted", message)
+                return "Omitted", message, None
+            result = await self._run_child(call, parent, node_id, display, scope)
+            if result[0] == "Failed" and bound.fail_fast:
+                bound.closed = True  # before the slot goes to the next in line
+            return result
+        finally:
+            bound.release()
+
+    async def _run_child(self, call: Dict[str, Any], parent: str, node_id: str, display: str,
+                         scope: Scope) -> Result:
         tname = call.get("template")
         try:
             if call.get("when") is not None:
@@ -433,7 +528,17 @@ class WorkflowRun:
         )
         workdir = tempfile.mkdtemp(prefix="am-wf-") if needs_dir else None
         try:
-            ok, message, stdout = await self._exec(cmd, stdin, env, workdir, node)
+            held: List[Bound] = []
+            try:
+                # around the process only; a cancellation while waiting, or
+                # while running, unwinds through here and frees what is held
+                for bound in self._process_bounds:
+                    await bound.acquire()
+                    held.append(bound)
+                ok, message, stdout = await self._exec(cmd, stdin, env, workdir, node)
+            finally:
+                for bound in reversed(held):
+                    bound.release()
             if not ok:
                 return False, message, None
             params: Dict[str, str] = {}
@@ -533,6 +638,7 @@ class WorkflowRun:
             try:
                 await proc.wait()
                 await asyncio.wait([drained], timeout=_KILL_DRAIN_SECONDS)
+                await _group_gone(proc.pid)
             except asyncio.CancelledError:
                 pass
             raise
@@ -606,6 +712,20 @@ def _kill_group(proc: "asyncio.subprocess.Process") -> None:
         os.killpg(proc.pid, signal.SIGKILL)
     except (ProcessLookupError, PermissionError):
         pass
+
+
+async def _group_gone(pgid: int) -> None:
+    """After :func:`_kill_group`: wait, for ``_KILL_REAP_SECONDS`` at the
+    most, until the group has no member left, zombies included. The group
+    id stays taken for as long as it has one."""
+    loop = asyncio.get_running_loop()
+    give_up = loop.time() + _KILL_REAP_SECONDS
+    while loop.time() < give_up:
+        try:
+            os.killpg(pgid, 0)
+        except (ProcessLookupError, PermissionError):
+            return
+        await asyncio.sleep(0.05)
 
 
 async def _cancel_all(tasks: List["asyncio.Future[Any]"]) -> None:

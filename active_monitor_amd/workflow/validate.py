@@ -134,6 +134,25 @@ def _check_refs(where: str, obj: Any, inputs: Set[str], wf_params: Set[str],
             problems.append(f"{where}: unknown variable namespace in {{{{{ref}}}}}")
 
 
+def _positive_int(value: Any) -> bool:
+    return isinstance(value, int) and not isinstance(value, bool) and value >= 1
+
+
+def ignored_synchronization(spec: Dict[str, Any]) -> List[str]:
+    """What of ``synchronization`` the local engine does not act on, for one
+    warning: semaphores (they are backed by a ConfigMap) and anything at
+    template level. Mutexes at ``spec`` level are honoured by the engine."""
+    found: List[str] = []
+    sync = spec.get("synchronization")
+    if isinstance(sync, dict) and ("semaphore" in sync or "semaphores" in sync):
+        found.append("spec.synchronization semaphores are")
+    names = [str(t.get("name")) for t in spec.get("templates") or []
+             if isinstance(t, dict) and "synchronization" in t]
+    if names:
+        found.append(f"template-level synchronization ({', '.join(names)}) is")
+    return found
+
+
 def validate_workflow_spec(spec: Any) -> List[str]:
     """Problems that would stop ``spec`` from running locally; ``[]`` when
     it is clean."""
@@ -156,6 +175,12 @@ def validate_workflow_spec(spec: Any) -> List[str]:
     if on_exit is not None and on_exit not in templates:
         problems.append(f"onExit template {on_exit!r} not found")
 
+    if spec.get("parallelism") is not None and not _positive_int(spec["parallelism"]):
+        problems.append("spec.parallelism must be a positive integer")
+    priority = spec.get("priority")
+    if priority is not None and (isinstance(priority, bool) or not isinstance(priority, int)):
+        problems.append("spec.priority must be an integer")
+
     wf_params = _param_names((spec.get("arguments") or {}).get("parameters"))
     _check_refs("spec.arguments", spec.get("arguments"), set(), wf_params, set(), "", problems)
 
@@ -175,6 +200,9 @@ def validate_workflow_spec(spec: Any) -> List[str]:
             problems.append(
                 f"{where}: several bodies ({', '.join(bodies + foreign)}); expected exactly one"
             )
+
+        if tmpl.get("parallelism") is not None and not _positive_int(tmpl["parallelism"]):
+            problems.append(f"{where}: parallelism must be a positive integer")
 
         calls = _calls(tmpl)
         kind = "tasks" if "dag" in tmpl else ("steps" if "steps" in tmpl else "")
