@@ -11,6 +11,8 @@ framework's standalone ``--serve-api`` endpoint:
     amctl --server ... delete hc inline-hello -n health
     amctl --server ... logs hc inline-hello -n health
     amctl --server ... run hc inline-hello -n health --wait
+    amctl --server ... get wftmpl -n health
+    amctl --server ... get cwft
 
 ``run`` asks the controller to run a check now (docs/OPERATIONS.md, "Running
 a check on demand"); it is ``kubectl annotate --overwrite`` with a fresh
@@ -57,6 +59,14 @@ ALIASES = {
     "workflows": (WF_API_VERSION, "Workflow"),
     "events": ("v1", "Event"),
     "event": ("v1", "Event"),
+    "wftmpl": (WF_API_VERSION, "WorkflowTemplate"),
+    "workflowtemplate": (WF_API_VERSION, "WorkflowTemplate"),
+    "workflowtemplates": (WF_API_VERSION, "WorkflowTemplate"),
+    # cluster-scoped: -n is ignored
+    "cwft": (WF_API_VERSION, "ClusterWorkflowTemplate"),
+    "cwftmpl": (WF_API_VERSION, "ClusterWorkflowTemplate"),
+    "clusterworkflowtemplate": (WF_API_VERSION, "ClusterWorkflowTemplate"),
+    "clusterworkflowtemplates": (WF_API_VERSION, "ClusterWorkflowTemplate"),
 }
 
 
@@ -118,6 +128,13 @@ async def cmd_get(client: HttpClient, args) -> int:
             ["NAME", "STATUS", "AGE"],
             [[o["metadata"]["name"],
               (o.get("status") or {}).get("phase", "") or "<pending>",
+              _age(o["metadata"].get("creationTimestamp"))] for o in objs],
+        ))
+    elif kind in ("WorkflowTemplate", "ClusterWorkflowTemplate"):
+        print(_table(
+            ["NAME", "TEMPLATES", "AGE"],
+            [[o["metadata"]["name"],
+              str(len((o.get("spec") or {}).get("templates") or [])),
               _age(o["metadata"].get("creationTimestamp"))] for o in objs],
         ))
     else:

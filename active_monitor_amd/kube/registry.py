@@ -27,6 +27,8 @@ class ResourceInfo:
 _BUILTINS = [
     ResourceInfo(API_VERSION, "HealthCheck", "healthchecks", True),
     ResourceInfo(WF_API_VERSION, WF_KIND, WF_PLURAL, True),
+    ResourceInfo(WF_API_VERSION, "WorkflowTemplate", "workflowtemplates", True),
+    ResourceInfo(WF_API_VERSION, "ClusterWorkflowTemplate", "clusterworkflowtemplates", False),
     ResourceInfo("v1", "ServiceAccount", "serviceaccounts", True),
     ResourceInfo("v1", "Event", "events", True),
     ResourceInfo("v1", "Namespace", "namespaces", False),

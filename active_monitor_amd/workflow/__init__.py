@@ -9,7 +9,7 @@ from .engines import (
     never_complete,
 )
 from .logs import LogStore
-from .validate import validate_workflow_spec
+from .validate import validate_template_library, validate_workflow_spec
 
 __all__ = [
     "POSTPONED_MESSAGE",
@@ -20,5 +20,6 @@ __all__ = [
     "always_fail",
     "always_succeed",
     "never_complete",
+    "validate_template_library",
     "validate_workflow_spec",
 ]

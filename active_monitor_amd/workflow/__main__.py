@@ -1,20 +1,29 @@
 """Offline workflow tools: ``python -m active_monitor_amd.workflow``.
 
-``lint FILE...``
-    Check Workflow or HealthCheck YAML against the surface the local executor
-    supports. A HealthCheck is first held against the CRD schema the way a
-    strict ``apply`` would (``invalid HealthCheck: spec.repeatAfterSec: ...``,
-    ``invalid HealthCheck: unknown field "spec.x"``); a cron schedule the
-    controller would use is parsed (``invalid HealthCheck: spec.schedule.cron:
-    ...``); then its inline check and remedy workflows are linted. Prints one
-    line per problem; exit status 1 when there are any.
+``lint FILE... [--templates PATH ...]``
+    Check Workflow, HealthCheck, WorkflowTemplate or ClusterWorkflowTemplate
+    YAML against the surface the local executor supports. The template
+    documents of all files given, and of every ``--templates`` file or
+    directory of YAML, are what ``templateRef`` and ``workflowTemplateRef``
+    are looked up in, by kind and name (a namespace means nothing offline); a
+    reference to none of them is a problem. A template document is itself
+    checked as a library: every template in it, ``entrypoint`` optional,
+    workflow parameters not required to be declared. A HealthCheck is first
+    held against the CRD schema the way a strict ``apply`` would (``invalid
+    HealthCheck: spec.repeatAfterSec: ...``, ``invalid HealthCheck: unknown
+    field "spec.x"``); a cron schedule the controller would use is parsed
+    (``invalid HealthCheck: spec.schedule.cron: ...``); then its inline check
+    and remedy workflows are linted. Prints one line per problem; exit status
+    1 when there are any.
 
-``run FILE [-p name=value ...] [--remedy] [--logs]``
+``run FILE [-p name=value ...] [--remedy] [--logs] [--templates PATH ...]``
     Execute one workflow with the local executor against a throw-away
-    in-memory store and print the phase and a node table. For a HealthCheck
-    the check workflow runs (``--remedy``: the remedy workflow). ``--logs``
-    adds what every leaf printed, stdout and stderr, under a ``--- NODE ---``
-    line each. Exit status 0 for ``Succeeded``, 1 for ``Failed``.
+    in-memory store and print the phase and a node table: the first Workflow
+    or HealthCheck workflow of FILE. The template documents of FILE and of
+    ``--templates`` are put into that store first. For a HealthCheck the
+    check workflow runs (``--remedy``: the remedy workflow). ``--logs`` adds
+    what every leaf printed, stdout and stderr, under a ``--- NODE ---`` line
+    each. Exit status 0 for ``Succeeded``, 1 for ``Failed``.
 
 ``next (FILE | --cron SPEC) [-n N] [--from RFC3339] [--time-zone ZONE]``
     Print the next N (default 5) activations of a cron schedule, one per
@@ -30,6 +39,7 @@ from __future__ import annotations
 
 import argparse
 import asyncio
+import os
 import sys
 from datetime import datetime, timezone
 from typing import Any, Dict, Iterator, List, Optional, Tuple
@@ -48,6 +58,10 @@ from ..kube.errors import NotFoundError
 from ..kube.registry import WF_API_VERSION, WF_KIND
 from . import LocalWorkflowEngine, validate_workflow_spec
 from .logs import LogStore
+from .templates import CWFT_KIND, TEMPLATE_KINDS, lookup_in
+from .validate import validate_template_library
+
+Templates = Dict[Tuple[bool, str], Dict[str, Any]]
 
 
 def _inline(wf: Any) -> bool:
@@ -74,11 +88,43 @@ def _schema_problems(doc: Dict[str, Any]) -> List[str]:
     return [f'invalid HealthCheck: unknown field "{p}"' for p in pruned]
 
 
-def _specs(path: str) -> Iterator[Tuple[str, Optional[Dict[str, Any]], List[str]]]:
-    """``(label, spec, problems)`` for every workflow found in ``path``."""
+def _load(path: str) -> List[Any]:
+    with open(path) as f:
+        return [d for d in yaml.safe_load_all(f) if d is not None]
+
+
+def _template_set(files: List[str], extra: List[str]) -> Templates:
+    """Every template document of ``files`` and of ``extra`` (files, or
+    directories whose ``*.yaml`` / ``*.yml`` are read), by (cluster scope,
+    name). A file that cannot be read is skipped here: as one of ``files``
+    it is reported when it is linted itself."""
+    paths = list(files)
+    for p in extra:
+        if os.path.isdir(p):
+            paths += sorted(os.path.join(p, n) for n in os.listdir(p)
+                            if n.endswith((".yaml", ".yml")))
+        else:
+            paths.append(p)
+    found: Templates = {}
+    for path in paths:
+        try:
+            docs = _load(path)
+        except (OSError, yaml.YAMLError):
+            continue
+        for doc in docs:
+            if isinstance(doc, dict) and doc.get("kind") in TEMPLATE_KINDS:
+                name = (doc.get("metadata") or {}).get("name")
+                if isinstance(name, str):
+                    found[(doc["kind"] == CWFT_KIND, name)] = doc
+    return found
+
+
+def _specs(path: str, templates: Optional[Templates] = None
+           ) -> Iterator[Tuple[str, Optional[Dict[str, Any]], List[str]]]:
+    """``(label, spec, problems)`` for every workflow found in ``path``; a
+    template document yields its problems as a library and no spec."""
     try:
-        with open(path) as f:
-            docs = [d for d in yaml.safe_load_all(f) if d is not None]
+        docs = _load(path)
     except (OSError, yaml.YAMLError) as e:
         yield path, None, [str(e)]
         return
@@ -120,16 +166,22 @@ def _specs(path: str) -> Iterator[Tuple[str, Optional[Dict[str, Any]], List[str]
                     yield f"{label} ({what})", None, [str(e)]
             if not found:
                 yield label, None, []  # file/URL sources: nothing to lint offline
+        elif kind in TEMPLATE_KINDS:
+            yield label, None, validate_template_library(
+                doc, lookup_in(templates) if templates is not None else None)
         else:
-            yield label, None, [f"expected kind Workflow or HealthCheck, found {kind!r}"]
+            yield label, None, [
+                "expected kind Workflow, HealthCheck, WorkflowTemplate or "
+                f"ClusterWorkflowTemplate, found {kind!r}"]
 
 
-def lint(paths: List[str]) -> int:
+def lint(paths: List[str], templates: Optional[List[str]] = None) -> int:
+    library = _template_set(paths, templates or [])
     bad = 0
     for path in paths:
-        for label, spec, problems in _specs(path):
+        for label, spec, problems in _specs(path, library):
             if spec is not None and not problems:
-                problems = validate_workflow_spec(spec)
+                problems = validate_workflow_spec(spec, lookup_in(library))
             for p in problems:
                 print(f"{label}: {p}")
             bad += len(problems)
@@ -138,9 +190,14 @@ def lint(paths: List[str]) -> int:
     return 1 if bad else 0
 
 
-async def _execute(spec: Dict[str, Any], name: str,
-                   logs: Optional[LogStore] = None) -> Dict[str, Any]:
+async def _execute(spec: Dict[str, Any], name: str, logs: Optional[LogStore] = None,
+                   templates: Optional[Templates] = None) -> Dict[str, Any]:
     client = MemoryClient(MemoryApiServer())
+    for doc in (templates or {}).values():
+        # offline a template's namespace means nothing: it goes where the
+        # Workflow goes
+        await client.create({**doc, "metadata": {
+            "name": doc["metadata"]["name"], "namespace": "local"}})
     engine = LocalWorkflowEngine(client, ttl_seconds=None, logs=logs)
     sub = client.watch(WF_API_VERSION, WF_KIND, "local")
     await engine.start()
@@ -183,12 +240,14 @@ def _print_nodes(status: Dict[str, Any]) -> None:
         print(f"{name:<{width}}  {type_:<9}  {phase:<9}  {message}".rstrip())
 
 
-async def _execute_with_logs(spec: Dict[str, Any], name: str) -> Tuple[Dict[str, Any], bytes]:
+async def _execute_with_logs(spec: Dict[str, Any], name: str,
+                             templates: Optional[Templates] = None
+                             ) -> Tuple[Dict[str, Any], bytes]:
     """``_execute`` over a temporary log store; also returns the log of
     every Pod node, in start order, under a ``--- displayName ---`` line."""
     logs = LogStore()
     try:
-        status = await _execute(spec, name, logs)
+        status = await _execute(spec, name, logs, templates)
         out: List[bytes] = []
         for node in (status.get("nodes") or {}).values():
             if node.get("type") != "Pod" or not logs.has_run("local", name):
@@ -204,10 +263,12 @@ async def _execute_with_logs(spec: Dict[str, Any], name: str) -> Tuple[Dict[str,
         logs.close()
 
 
-def run(path: str, params: List[str], remedy: bool, logs: bool = False) -> int:
+def run(path: str, params: List[str], remedy: bool, logs: bool = False,
+        templates: Optional[List[str]] = None) -> int:
     wanted = "(remedyworkflow)" if remedy else "(workflow)"
     found: List[Tuple[str, Dict[str, Any]]] = []
-    for label, spec, problems in _specs(path):
+    library = _template_set([path], templates or [])
+    for label, spec, problems in _specs(path, library):
         if problems:
             print(f"{label}: {problems[0]}")
             return 1
@@ -236,9 +297,9 @@ def run(path: str, params: List[str], remedy: bool, logs: bool = False) -> int:
         args["parameters"] = declared + [{"name": k, "value": v} for k, v in overrides.items()]
     log_text = b""
     if logs:
-        status, log_text = asyncio.run(_execute_with_logs(chosen, "run"))
+        status, log_text = asyncio.run(_execute_with_logs(chosen, "run", library))
     else:
-        status = asyncio.run(_execute(chosen, "run"))
+        status = asyncio.run(_execute(chosen, "run", templates=library))
     print(f"phase: {status['phase']}")
     if status.get("message"):
         print(f"message: {status['message']}")
@@ -304,8 +365,13 @@ def main(argv: Optional[List[str]] = None) -> int:
         description="Lint or run workflows with the local executor; no server needed.",
     )
     sub = ap.add_subparsers(dest="cmd", required=True)
-    p_lint = sub.add_parser("lint", help="check Workflow / HealthCheck YAML")
+    p_lint = sub.add_parser(
+        "lint", help="check Workflow / HealthCheck / WorkflowTemplate YAML")
     p_lint.add_argument("files", nargs="+", metavar="FILE")
+    shared = dict(action="append", default=[], metavar="PATH",
+                  help="a file, or a directory of YAML, whose WorkflowTemplates and "
+                       "ClusterWorkflowTemplates references are looked up in (repeatable)")
+    p_lint.add_argument("--templates", **shared)
     p_run = sub.add_parser("run", help="execute one workflow locally")
     p_run.add_argument("file", metavar="FILE")
     p_run.add_argument("-p", "--parameter", action="append", default=[], metavar="name=value",
@@ -314,6 +380,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                        help="for a HealthCheck, run its remedy workflow instead of the check")
     p_run.add_argument("--logs", action="store_true",
                        help="after the node table, print what each leaf printed")
+    p_run.add_argument("--templates", **shared)
     p_next = sub.add_parser("next", help="print a cron schedule's next activations")
     what = p_next.add_mutually_exclusive_group(required=True)
     what.add_argument("file", nargs="?", metavar="FILE",
@@ -329,10 +396,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                              "as the controller's --cron-time-zone")
     args = ap.parse_args(argv)
     if args.cmd == "lint":
-        return lint(args.files)
+        return lint(args.files, args.templates)
     if args.cmd == "next":
         return next_activations(args.file, args.cron, args.n, args.start, args.time_zone)
-    return run(args.file, args.parameter, args.remedy, args.logs)
+    return run(args.file, args.parameter, args.remedy, args.logs, args.templates)
 
 
 if __name__ == "__main__":

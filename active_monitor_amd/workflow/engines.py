@@ -30,6 +30,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 from ..kube.client import KubeClient
 from ..kube.errors import ConflictError, NotFoundError
 from ..kube.registry import WF_API_VERSION, WF_KIND
+from .templates import CWFT_KIND, WFT_KIND, has_references, resolve
 
 log = logging.getLogger("active_monitor_amd.workflow")
 
@@ -245,7 +246,13 @@ class _EngineBase:
         key = f'{prefix}{(wf["metadata"].get("namespace", ""))}/{wf["metadata"]["name"]}'
         task = asyncio.ensure_future(coro)
         self._inflight[key] = task
-        task.add_done_callback(lambda t, k=key: self._inflight.pop(k, None))
+
+        def done(t: "asyncio.Future[Any]", k: str = key) -> None:
+            # a later task may have taken the key: that one stays
+            if self._inflight.get(k) is t:
+                del self._inflight[k]
+
+        task.add_done_callback(done)
         return task
 
     # -- admission --------------------------------------------------------
@@ -274,7 +281,7 @@ class _EngineBase:
         """Run ``wf`` now, or queue it when a limit or a mutex may stand in
         its way. ``recovering``: only queue it, start() admits once all that
         it found is queued."""
-        spec = wf.get("spec")
+        spec = self._spec_of(wf)
         names = mutex_names(spec) if isinstance(spec, dict) and "synchronization" in spec else None
         if not self._limited and not names:
             self._spawn(wf, self._run(wf))
@@ -294,6 +301,11 @@ class _EngineBase:
             self._pump()
             if key in self._queued:
                 self._postpone(entry)
+
+    def _spec_of(self, wf: Dict[str, Any]) -> Any:
+        """The spec that admission reads: priority, mutexes, the deadline
+        that runs in the queue."""
+        return wf.get("spec")
 
     def _blocked_by(self, entry: _Queued) -> Optional[str]:
         """The ``Pending`` message for what keeps ``entry`` from starting
@@ -357,7 +369,8 @@ class _EngineBase:
             entry.postponed = self._spawn(
                 wf, self._set_status(wf, {"phase": "Pending", "message": message}),
                 "pending:")
-        deadline = (wf.get("spec") or {}).get("activeDeadlineSeconds")
+        spec = self._spec_of(wf)
+        deadline = spec.get("activeDeadlineSeconds") if isinstance(spec, dict) else None
         try:
             deadline = float(deadline) if deadline and deadline is not True else 0.0
         except (TypeError, ValueError):
@@ -570,6 +583,10 @@ class LocalWorkflowEngine(_EngineBase):
       README.md:275-285);
     - ``retryStrategy`` with ``limit`` and ``backoff``;
     - ``spec.onExit`` with ``{{workflow.status}}``;
+    - shared templates: ``templateRef`` on steps and tasks and
+      ``spec.workflowTemplateRef``, resolved once per Workflow from a
+      watch-fed cache of WorkflowTemplates and ClusterWorkflowTemplates, before
+      admission reads the spec (:mod:`.templates`);
     - workflow-level ``activeDeadlineSeconds``. Every leaf runs in its own
       process group, which is killed when the deadline passes or the engine
       stops.
@@ -596,17 +613,157 @@ class LocalWorkflowEngine(_EngineBase):
         #: a :class:`~.logs.LogStore` for what the leaves print, or None;
         #: whoever built it closes it
         self.logs = logs
+        # shared templates, fed by a watch per kind: (cluster scope,
+        # namespace or "", name) → object. Objects are replaced, never
+        # changed in place, so a run keeps what it resolved against.
+        self._templates: Dict[Tuple[bool, str, str], Dict[str, Any]] = {}
+        self._template_subs: List[Any] = []
+        self._template_tasks: List["asyncio.Future[Any]"] = []
+        #: what :meth:`_submit` resolved, until :meth:`_run` takes it
+        self._resolved: Dict[str, Any] = {}
+        #: direct reads made for a name the cache did not have
+        self.template_reads = 0
+
+    async def start(self) -> None:
+        # the cache is whole before the first Workflow is looked at; watch
+        # first, then list, so that nothing created in between is missed
+        for kind, namespace in ((WFT_KIND, self.namespace), (CWFT_KIND, None)):
+            sub = self.client.watch(WF_API_VERSION, kind, namespace)
+            self._template_subs.append(sub)
+            for obj in await self.client.list(WF_API_VERSION, kind, namespace):
+                self._cache_template(obj)
+            self._template_tasks.append(asyncio.ensure_future(self._follow_templates(sub)))
+        await super().start()
+
+    @staticmethod
+    def _template_key(obj: Dict[str, Any]) -> Tuple[bool, str, str]:
+        meta = obj.get("metadata") or {}
+        cluster = obj.get("kind") == CWFT_KIND
+        return cluster, "" if cluster else meta.get("namespace", ""), meta.get("name", "")
+
+    def _cache_template(self, obj: Dict[str, Any]) -> None:
+        """Keep ``obj`` unless what is cached is newer (a direct read and
+        the watch may deliver the same object in either order)."""
+        key = self._template_key(obj)
+        have = self._templates.get(key)
+        if have is not None:
+            try:
+                if (int(have["metadata"]["resourceVersion"])
+                        > int(obj["metadata"]["resourceVersion"])):
+                    return
+            except (KeyError, TypeError, ValueError):
+                pass  # opaque resourceVersion: the later arrival stands
+        self._templates[key] = obj
+
+    async def _follow_templates(self, sub: Any) -> None:
+        async for ev in sub:
+            if ev["type"] == "DELETED":
+                self._templates.pop(self._template_key(ev["object"]), None)
+            elif ev["type"] in ("ADDED", "MODIFIED"):
+                self._cache_template(ev["object"])
+
+    def _resolve(self, wf: Dict[str, Any]) -> Any:
+        """``wf``'s spec resolved against the cache; namespaced names are
+        looked up in the Workflow's namespace."""
+        ns = wf["metadata"].get("namespace", "")
+        return resolve(wf["spec"], lambda cluster, name: self._templates.get(
+            (cluster, "" if cluster else ns, name)))
+
+    def cached_templates(self) -> List[str]:
+        """What the cache holds, sorted: ``namespaced/NAMESPACE/NAME`` and
+        ``cluster/NAME``."""
+        return sorted(f"cluster/{name}" if cluster else f"namespaced/{ns}/{name}"
+                      for cluster, ns, name in self._templates)
+
+    def cached_template(self, name: str, namespace: str = "",
+                        cluster: bool = False) -> Optional[Dict[str, Any]]:
+        """The cached object of that name, None when there is none; read-only."""
+        return self._templates.get((cluster, "" if cluster else namespace, name))
+
+    def _submit(self, wf: Dict[str, Any], recovering: bool = False) -> None:
+        # this runs in the watch loop: whatever one Workflow's spec holds,
+        # the Workflows after it are still looked at
+        try:
+            found = self._resolve(wf) if has_references(wf.get("spec")) else None
+        except Exception:
+            log.exception("workflow %s/%s: references not resolved, taken as it is",
+                          wf["metadata"].get("namespace", ""), wf["metadata"].get("name"))
+            found = None
+        if found is None:
+            super()._submit(wf, recovering)
+            return
+        if found.missing:
+            self._spawn(wf, self._confirm_missing(wf, found), "resolve:")
+            return
+        self._take_up(wf, found, recovering)
+
+    def _take_up(self, wf: Dict[str, Any], found: Any, recovering: bool = False) -> None:
+        meta = wf["metadata"]
+        self._resolved[f'{meta.get("namespace", "")}/{meta["name"]}'] = found
+        if found.errors:
+            self._spawn(wf, self._run(wf))  # fails at once: nothing to wait for
+        else:
+            super()._submit(wf, recovering)
+
+    async def _confirm_missing(self, wf: Dict[str, Any], found: Any) -> None:
+        """A name the cache lacks is read once from the apiserver before the
+        Workflow is failed for it: a template applied in the same instant as
+        its user may not have come down the watch yet. The task is cancelled
+        when the Workflow is deleted meanwhile (:meth:`_deleted`).
+
+        A Workflow recovered at start that comes through here is admitted
+        when its reads are done, not in the ordered pass over what start()
+        found; the cache was primed by a list just before, so this takes a
+        template created in that very moment."""
+        ns = wf["metadata"].get("namespace", "")
+        asked: set = set()
+        while True:
+            wanted = [m for m in found.missing if m not in asked]
+            if not wanted:
+                break
+            for cluster, name in wanted:
+                asked.add((cluster, name))
+                self.template_reads += 1
+                try:
+                    self._cache_template(await self.client.get(
+                        WF_API_VERSION, CWFT_KIND if cluster else WFT_KIND,
+                        "" if cluster else ns, name))
+                except NotFoundError:
+                    pass
+            found = self._resolve(wf)
+        if not self._stopping:
+            self._take_up(wf, found)
+
+    def _spec_of(self, wf: Dict[str, Any]) -> Any:
+        meta = wf["metadata"]
+        found = self._resolved.get(f'{meta.get("namespace", "")}/{meta["name"]}')
+        return found.spec if found is not None else wf.get("spec")
 
     def _processes(self) -> int:
         return self.process_slots.held
 
     def _deleted(self, wf: Dict[str, Any]) -> None:
+        meta = wf["metadata"]
+        key = f'{meta.get("namespace", "")}/{meta["name"]}'
+        self._resolved.pop(key, None)
+        confirming = self._inflight.get(f"resolve:{key}")
+        if confirming is not None:
+            confirming.cancel()  # not taken up: there is nothing to run any more
         if self.logs is not None:
-            meta = wf["metadata"]
             self.logs.discard(meta.get("namespace", ""), meta["name"])
+
+    async def _fail_expired(self, entry: _Queued) -> None:
+        self._resolved.pop(entry.key, None)
+        await super()._fail_expired(entry)
 
     async def stop(self) -> None:
         inflight = list(self._inflight.values())
+        for sub in self._template_subs:
+            sub.close()
+        for task in self._template_tasks:
+            task.cancel()
+        await asyncio.gather(*self._template_tasks, return_exceptions=True)
+        self._template_subs, self._template_tasks = [], []
         await super().stop()
         # cancelled runs kill and reap their process groups before they end
         if inflight:
@@ -616,9 +773,18 @@ class LocalWorkflowEngine(_EngineBase):
         from .executor import WorkflowRun
         from .validate import ignored_synchronization, validate_workflow_spec
 
-        spec = wf.get("spec") or {}
         meta = wf["metadata"]
         ns, name = meta.get("namespace", ""), meta["name"]
+        # resolved once, when the Workflow was taken up: the run reads this
+        # snapshot, whatever happens to the shared templates meanwhile
+        found = self._resolved.pop(f"{ns}/{name}", None)
+        spec = (found.spec if found is not None else wf.get("spec")) or {}
+        recorded: Dict[str, Any] = {}
+        if found is not None and not found.errors:
+            if found.stored_spec is not None:
+                recorded["storedWorkflowTemplateSpec"] = found.stored_spec
+            if found.stored:
+                recorded["storedTemplates"] = found.stored
         logs = self.logs
         if logs is not None:
             try:
@@ -626,18 +792,22 @@ class LocalWorkflowEngine(_EngineBase):
             except (OSError, ValueError) as e:
                 log.warning("no logs kept for workflow %s/%s: %s", ns, name, e)
                 logs = None
-        await self._set_status(wf, {"phase": "Running", "startedAt": _now_iso()})
+        await self._set_status(wf, {"phase": "Running", "startedAt": _now_iso(), **recorded})
         nodes: Dict[str, Any] = {}
         outputs: List[Dict[str, Any]] = []
-        problems = validate_workflow_spec(spec)
+        if found is not None and found.errors:
+            problems = [found.errors[0][1]]
+        else:
+            problems = validate_workflow_spec(spec, found)
         if problems:
             phase, message = "Failed", problems[0]
         else:
-            ignored = ignored_synchronization(spec)
+            ignored = ignored_synchronization(spec, found)
             if ignored:
                 log.warning("workflow %s/%s: %s not supported and ignored",
                             ns, name, " and ".join(ignored))
-            run = WorkflowRun(spec, name, ns, logs=logs, process_slots=self.process_slots)
+            run = WorkflowRun(spec, name, ns, logs=logs, process_slots=self.process_slots,
+                              templates=found.scopes if found is not None else None)
             try:
                 phase, message, timed_out = await self._run_phases(run, spec)
             except asyncio.CancelledError:
@@ -648,7 +818,7 @@ class LocalWorkflowEngine(_EngineBase):
             nodes = run.nodes
             if not timed_out:  # a run that was cut short publishes no outputs
                 outputs = run.global_outputs
-        status: Dict[str, Any] = {"phase": phase, "finishedAt": _now_iso()}
+        status: Dict[str, Any] = {"phase": phase, "finishedAt": _now_iso(), **recorded}
         if message:
             status["message"] = message
         if outputs:

@@ -29,6 +29,7 @@ from .template import (
     substitute_list,
     to_str,
 )
+from .templates import OWN_SCOPE, scope_key, shown_ref
 from .validate import task_dependencies
 
 #: ``outputs.result`` keeps at most this many bytes of a leaf's stdout
@@ -57,6 +58,9 @@ Scope = Dict[str, str]
 Outputs = Dict[str, Any]  # {"result": str, "parameters": {name: value}}
 #: (phase, message, outputs); outputs is None for skipped / fanned-out calls
 Result = Tuple[str, str, Optional[Outputs]]
+#: the template a call names: (scope, template name, the ``templateRef`` its
+#: node shows or None for a ``template:`` call); scopes as in :mod:`.templates`
+Target = Tuple[str, Any, Optional[Dict[str, Any]]]
 
 
 def _now_iso() -> str:
@@ -119,7 +123,10 @@ def _parallelism_bound(tmpl: Dict[str, Any]) -> Optional[Bound]:
 
 class WorkflowRun:
     def __init__(self, spec: Dict[str, Any], name: str, namespace: str,
-                 logs: Any = None, process_slots: Optional[Bound] = None):
+                 logs: Any = None, process_slots: Optional[Bound] = None,
+                 templates: Optional[Dict[str, Dict[Any, Dict[str, Any]]]] = None):
+        """``spec`` is the effective spec; ``templates`` the shared templates
+        it reaches, by scope (:attr:`.templates.Resolved.scopes`)."""
         self.spec = spec
         # a leaf process holds one slot of each, taken in this order:
         # spec.parallelism, then the engine's bound over all of its runs
@@ -132,6 +139,7 @@ class WorkflowRun:
         #: and dropped
         self.logs = logs
         self.templates = {t.get("name"): t for t in spec.get("templates") or []}
+        self._scopes = {**(templates or {}), OWN_SCOPE: self.templates}
         self.nodes: Dict[str, Dict[str, Any]] = {}
         self.global_outputs: List[Dict[str, str]] = []
         self._procs: Dict[int, asyncio.subprocess.Process] = {}
@@ -154,7 +162,7 @@ class WorkflowRun:
 
     async def _run_root(self, template: str, node_id: str, scope: Scope) -> Tuple[str, str]:
         phase, message, _ = await self._run_template(
-            template, self.arguments, node_id, node_id, None, scope
+            (OWN_SCOPE, template, None), self.arguments, node_id, node_id, None, scope
         )
         return phase, message
 
@@ -170,14 +178,29 @@ class WorkflowRun:
 
     # -- nodes ------------------------------------------------------------
 
-    def _open(self, node_id: str, display: str, type_: str, template: Optional[str],
+    @staticmethod
+    def _target(call: Dict[str, Any], tscope: str) -> Target:
+        """What a step or task of a template of scope ``tscope`` names."""
+        ref = call.get("templateRef")
+        if isinstance(ref, dict):
+            return (scope_key(ref.get("clusterScope") is True, ref.get("name")),
+                    ref.get("template"), shown_ref(ref))
+        return tscope, call.get("template"), None
+
+    def _open(self, node_id: str, display: str, type_: str, target: Optional[Target],
               parent: Optional[str]) -> Dict[str, Any]:
         node: Dict[str, Any] = {
             "id": node_id, "displayName": display, "type": type_,
             "startedAt": _now_iso(), "children": [],
         }
-        if template is not None:
-            node["templateName"] = template
+        if target is not None:
+            tscope, template, ref = target
+            if ref is not None:
+                node["templateRef"] = ref
+            elif template is not None:
+                node["templateName"] = template
+            if tscope:
+                node["templateScope"] = tscope
         self.nodes[node_id] = node
         if parent is not None and parent in self.nodes:
             self.nodes[parent]["children"].append(node_id)
@@ -200,10 +223,10 @@ class WorkflowRun:
             if shown:
                 node["outputs"] = shown
 
-    def _mark(self, node_id: str, display: str, template: Optional[str], parent: Optional[str],
-              phase: str, message: str) -> None:
+    def _mark(self, node_id: str, display: str, target: Optional[Target],
+              parent: Optional[str], phase: str, message: str) -> None:
         """A node that never ran: ``Skipped`` (false ``when``) or ``Omitted``."""
-        self._close(self._open(node_id, display, "Skipped", template, parent), phase, message)
+        self._close(self._open(node_id, display, "Skipped", target, parent), phase, message)
 
     # -- templates --------------------------------------------------------
 
@@ -228,14 +251,15 @@ class WorkflowRun:
             out[f"inputs.parameters.{name}"] = value
         return out
 
-    async def _run_template(self, tname: Any, args: Dict[str, str], node_id: str, display: str,
-                            parent: Optional[str], wf_scope: Scope) -> Result:
-        tmpl = self.templates.get(tname) or {}
+    async def _run_template(self, target: Target, args: Dict[str, str], node_id: str,
+                            display: str, parent: Optional[str], wf_scope: Scope) -> Result:
+        tmpl = (self._scopes.get(target[0]) or {}).get(target[1]) or {}
         retry = tmpl.get("retryStrategy")
         if not isinstance(retry, dict):
-            return await self._run_once(tmpl, args, node_id, display, parent, wf_scope, None)
+            return await self._run_once(tmpl, target, args, node_id, display, parent,
+                                        wf_scope, None)
 
-        node = self._open(node_id, display, "Retry", tname, parent)
+        node = self._open(node_id, display, "Retry", target, parent)
         try:
             limit = int(str(substitute(retry.get("limit") or 0, wf_scope)).strip() or 0)
             backoff = retry.get("backoff") if isinstance(retry.get("backoff"), dict) else None
@@ -253,8 +277,8 @@ class WorkflowRun:
         attempt = 0
         while True:
             phase, message, outputs = await self._run_once(
-                tmpl, args, f"{node_id}({attempt})", f"{display}({attempt})", node_id,
-                wf_scope, attempt,
+                tmpl, target, args, f"{node_id}({attempt})", f"{display}({attempt})",
+                node_id, wf_scope, attempt,
             )
             if phase == "Succeeded" or attempt >= limit:
                 break
@@ -269,10 +293,10 @@ class WorkflowRun:
         self._close(node, phase, message, outputs)
         return phase, message, outputs
 
-    async def _run_once(self, tmpl: Dict[str, Any], args: Dict[str, str], node_id: str,
-                        display: str, parent: Optional[str], wf_scope: Scope,
+    async def _run_once(self, tmpl: Dict[str, Any], target: Target, args: Dict[str, str],
+                        node_id: str, display: str, parent: Optional[str], wf_scope: Scope,
                         attempt: Optional[int]) -> Result:
-        tname = tmpl.get("name")
+        tscope = target[0]
         if "steps" in tmpl:
             type_ = "Steps"
         elif "dag" in tmpl:
@@ -281,16 +305,16 @@ class WorkflowRun:
             type_ = "Suspend"
         else:
             type_ = "Pod"
-        node = self._open(node_id, display, type_, tname, parent)
+        node = self._open(node_id, display, type_, (tscope, tmpl.get("name"), target[2]), parent)
         outputs: Optional[Outputs] = None
         try:
             scope = self._inputs(tmpl, args, wf_scope)
             if attempt is not None:
                 scope["retries"] = str(attempt)
             if type_ == "Steps":
-                ok, message = await self._run_steps(tmpl, node_id, scope)
+                ok, message = await self._run_steps(tmpl, node_id, scope, tscope)
             elif type_ == "DAG":
-                ok, message = await self._run_dag(tmpl, node_id, scope)
+                ok, message = await self._run_dag(tmpl, node_id, scope, tscope)
             elif type_ == "Suspend":
                 duration = substitute((tmpl["suspend"] or {}).get("duration", 0) or 0, scope)
                 await asyncio.sleep(parse_duration(duration))
@@ -344,7 +368,8 @@ class WorkflowRun:
 
     # -- steps and DAGs ---------------------------------------------------
 
-    async def _run_steps(self, tmpl: Dict[str, Any], node_id: str, scope: Scope) -> Tuple[bool, str]:
+    async def _run_steps(self, tmpl: Dict[str, Any], node_id: str, scope: Scope,
+                         tscope: str = OWN_SCOPE) -> Tuple[bool, str]:
         bound = _parallelism_bound(tmpl)
         for i, group in enumerate(tmpl["steps"] or []):
             steps = [s for s in (group if isinstance(group, list) else [group])
@@ -352,7 +377,7 @@ class WorkflowRun:
             gid = f"{node_id}[{i}]"
             gnode = self._open(gid, f"[{i}]", "StepGroup", None, node_id)
             results = await _gather([
-                self._run_call(s, "steps", gid, f"{gid}.{s.get('name')}", scope, bound)
+                self._run_call(s, "steps", gid, f"{gid}.{s.get('name')}", scope, bound, tscope)
                 for s in steps
             ])
             failed = [msg for phase, msg, _ in results if phase == "Failed"]
@@ -361,7 +386,8 @@ class WorkflowRun:
                 return False, failed[0]
         return True, ""
 
-    async def _run_dag(self, tmpl: Dict[str, Any], node_id: str, scope: Scope) -> Tuple[bool, str]:
+    async def _run_dag(self, tmpl: Dict[str, Any], node_id: str, scope: Scope,
+                       tscope: str = OWN_SCOPE) -> Tuple[bool, str]:
         dag = tmpl["dag"] or {}
         tasks = {t.get("name"): t for t in dag.get("tasks") or [] if isinstance(t, dict)}
         deps = {name: task_dependencies(t) for name, t in tasks.items()}
@@ -375,7 +401,7 @@ class WorkflowRun:
 
         def omit(name: str, why: str) -> None:
             phases[name] = "Omitted"
-            self._mark(f"{node_id}.{name}", name, tasks[name].get("template"), node_id,
+            self._mark(f"{node_id}.{name}", name, self._target(tasks[name], tscope), node_id,
                        "Omitted", why)
 
         try:
@@ -390,7 +416,8 @@ class WorkflowRun:
                         omit(name, "omitted: a dependency did not succeed")
                     elif all(s in ("Succeeded", "Skipped") for s in states):
                         fut = asyncio.ensure_future(self._run_call(
-                            tasks[name], "tasks", node_id, f"{node_id}.{name}", scope, bound
+                            tasks[name], "tasks", node_id, f"{node_id}.{name}", scope, bound,
+                            tscope,
                         ))
                         running[fut] = name
                 if not running:
@@ -412,14 +439,17 @@ class WorkflowRun:
         return True, ""
 
     async def _run_call(self, call: Dict[str, Any], kind: str, parent: str, node_id: str,
-                        scope: Scope, bound: Optional[Bound] = None) -> Result:
+                        scope: Scope, bound: Optional[Bound] = None,
+                        tscope: str = OWN_SCOPE) -> Result:
         """One step or DAG task: loop expansion, ``when``, arguments, then
         the template it names. Publishes ``steps.NAME.*`` / ``tasks.NAME.*``
         into the caller's scope when it ran exactly once. ``bound`` is the
         calling template's ``parallelism``: the call, or each item of its
-        loop, holds one slot of it from start to end."""
+        loop, holds one slot of it from start to end. ``tscope`` is the
+        calling template's scope, where a ``template:`` of the call is looked
+        up."""
         name = str(call.get("name"))
-        tname = call.get("template")
+        target = self._target(call, tscope)
         try:
             if "withItems" in call or "withParam" in call:
                 if "withItems" in call:
@@ -430,7 +460,7 @@ class WorkflowRun:
                     items = parse_with_param(substitute(to_str(call["withParam"]), scope))
                 results = await _gather([
                     self._run_expanded(
-                        call, parent, f"{parent}.{item_display_name(name, i, item)}",
+                        call, target, parent, f"{parent}.{item_display_name(name, i, item)}",
                         item_display_name(name, i, item), {**scope, **item_scope(item)},
                         bound,
                     )
@@ -446,9 +476,9 @@ class WorkflowRun:
                 scope[f"{kind}.{name}.status"] = phase
                 return phase, failed[0] if failed else "", None
             phase, message, outputs = await self._run_expanded(
-                call, parent, node_id, name, scope, bound)
+                call, target, parent, node_id, name, scope, bound)
         except TemplateError as e:
-            self._mark(node_id, name, tname, parent, "Failed", str(e))
+            self._mark(node_id, name, target, parent, "Failed", str(e))
             return "Failed", str(e), None
         scope[f"{kind}.{name}.status"] = phase
         if phase == "Succeeded" and outputs:
@@ -458,41 +488,41 @@ class WorkflowRun:
                 scope[f"{kind}.{name}.outputs.parameters.{k}"] = v
         return phase, message, outputs
 
-    async def _run_expanded(self, call: Dict[str, Any], parent: str, node_id: str, display: str,
-                            scope: Scope, bound: Optional[Bound] = None) -> Result:
+    async def _run_expanded(self, call: Dict[str, Any], target: Target, parent: str,
+                            node_id: str, display: str, scope: Scope,
+                            bound: Optional[Bound] = None) -> Result:
         if bound is None:
-            return await self._run_child(call, parent, node_id, display, scope)
+            return await self._run_child(call, target, parent, node_id, display, scope)
         await bound.acquire()
         try:
             if bound.closed:
                 message = "omitted: the DAG failed before this task could start"
-                self._mark(node_id, display, call.get("template"), parent, "Omitted", message)
+                self._mark(node_id, display, target, parent, "Omitted", message)
                 return "Omitted", message, None
-            result = await self._run_child(call, parent, node_id, display, scope)
+            result = await self._run_child(call, target, parent, node_id, display, scope)
             if result[0] == "Failed" and bound.fail_fast:
                 bound.closed = True  # before the slot goes to the next in line
             return result
         finally:
             bound.release()
 
-    async def _run_child(self, call: Dict[str, Any], parent: str, node_id: str, display: str,
-                         scope: Scope) -> Result:
-        tname = call.get("template")
+    async def _run_child(self, call: Dict[str, Any], target: Target, parent: str,
+                         node_id: str, display: str, scope: Scope) -> Result:
         try:
             if call.get("when") is not None:
                 expr = substitute(to_str(call["when"]), scope)
                 if not eval_when(expr):
                     message = f"when {expr!r} evaluated false"
-                    self._mark(node_id, display, tname, parent, "Skipped", message)
+                    self._mark(node_id, display, target, parent, "Skipped", message)
                     return "Skipped", message, None
             args: Dict[str, str] = {}
             for p in (call.get("arguments") or {}).get("parameters") or []:
                 if isinstance(p, dict) and p.get("name") is not None and p.get("value") is not None:
                     args[str(p["name"])] = substitute(to_str(p["value"]), scope)
         except TemplateError as e:
-            self._mark(node_id, display, tname, parent, "Failed", str(e))
+            self._mark(node_id, display, target, parent, "Failed", str(e))
             return "Failed", str(e), None
-        return await self._run_template(tname, args, node_id, display, parent, scope)
+        return await self._run_template(target, args, node_id, display, parent, scope)
 
     # -- leaves -----------------------------------------------------------
 

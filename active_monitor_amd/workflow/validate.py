@@ -11,6 +11,18 @@ import re
 from typing import Any, Dict, List, Optional, Set
 
 from .template import find_refs, find_strings
+from .templates import (
+    OWN_SCOPE,
+    Lookup,
+    Resolved,
+    calls_of,
+    library_scope,
+    resolve,
+    resolve_library,
+    scope_label,
+    template_where,
+    well_formed_ref,
+)
 
 #: template body types the local executor runs
 BODY_TYPES = ("container", "script", "steps", "dag", "suspend")
@@ -47,20 +59,6 @@ def _param_names(params: Any) -> Set[str]:
     }
 
 
-def _calls(tmpl: Dict[str, Any]) -> List[Dict[str, Any]]:
-    """The steps or DAG tasks of a composite template, flattened."""
-    if "steps" in tmpl:
-        out = []
-        for group in tmpl.get("steps") or []:
-            for s in group if isinstance(group, list) else [group]:
-                if isinstance(s, dict):
-                    out.append(s)
-        return out
-    if "dag" in tmpl:
-        return [t for t in ((tmpl.get("dag") or {}).get("tasks") or []) if isinstance(t, dict)]
-    return []
-
-
 def _find_cycle(deps: Dict[str, List[str]]) -> Optional[str]:
     """Name of a task that sits on a dependency cycle, or None."""
     WHITE, GREY, BLACK = 0, 1, 2
@@ -87,11 +85,13 @@ def _find_cycle(deps: Dict[str, List[str]]) -> Optional[str]:
     return None
 
 
-def _check_refs(where: str, obj: Any, inputs: Set[str], wf_params: Set[str],
+def _check_refs(where: str, obj: Any, inputs: Set[str], wf_params: Optional[Set[str]],
                 call_names: Set[str], kind: str, problems: List[str],
                 in_loop: bool = False) -> None:
     """``in_loop``: ``obj`` is a step or task that carries ``withItems`` /
-    ``withParam`` — the only place where ``{{item}}`` means anything."""
+    ``withParam`` — the only place where ``{{item}}`` means anything.
+    ``wf_params`` None: workflow parameters are not known here (a template
+    document checked on its own) and any name passes."""
     for text in find_strings(obj):
         if "{{=" in text.replace(" ", ""):
             problems.append(f"{where}: expression tags ({{{{=...}}}}) are not supported")
@@ -107,7 +107,7 @@ def _check_refs(where: str, obj: Any, inputs: Set[str], wf_params: Set[str],
                 )
         elif head == "workflow":
             if rest.startswith("parameters."):
-                if rest[len("parameters."):] not in wf_params:
+                if wf_params is not None and rest[len("parameters."):] not in wf_params:
                     problems.append(
                         f"{where}: {{{{{ref}}}}} refers to an undeclared workflow parameter"
                     )
@@ -138,41 +138,171 @@ def _positive_int(value: Any) -> bool:
     return isinstance(value, int) and not isinstance(value, bool) and value >= 1
 
 
-def ignored_synchronization(spec: Dict[str, Any]) -> List[str]:
+def ignored_synchronization(spec: Dict[str, Any],
+                            templates: Optional[Resolved] = None) -> List[str]:
     """What of ``synchronization`` the local engine does not act on, for one
     warning: semaphores (they are backed by a ConfigMap) and anything at
-    template level. Mutexes at ``spec`` level are honoured by the engine."""
+    template level, in the spec's own templates and, with ``templates``, in
+    the shared ones it reaches. Mutexes at ``spec`` level are honoured by
+    the engine."""
     found: List[str] = []
     sync = spec.get("synchronization")
     if isinstance(sync, dict) and ("semaphore" in sync or "semaphores" in sync):
         found.append("spec.synchronization semaphores are")
     names = [str(t.get("name")) for t in spec.get("templates") or []
              if isinstance(t, dict) and "synchronization" in t]
+    if templates is not None:
+        names += [key for key, t in templates.stored.items() if "synchronization" in t]
     if names:
         found.append(f"template-level synchronization ({', '.join(names)}) is")
     return found
 
 
-def validate_workflow_spec(spec: Any) -> List[str]:
-    """Problems that would stop ``spec`` from running locally; ``[]`` when
-    it is clean."""
-    if not isinstance(spec, dict):
-        return ["workflow spec is not a map"]
-    problems: List[str] = []
-    templates: Dict[str, Dict[str, Any]] = {}
-    for t in spec.get("templates") or []:
-        if not isinstance(t, dict) or t.get("name") is None:
-            problems.append("a template has no name")
+UNRESOLVABLE = "cannot be resolved here: no WorkflowTemplates were given"
+
+
+def _check_template(where: str, tmpl: Dict[str, Any], local: Dict[Any, Dict[str, Any]],
+                    resolvable: bool, wf_params: Optional[Set[str]],
+                    problems: List[str]) -> None:
+    """One template in its own scope: ``local`` holds the templates that a
+    ``template: X`` of its calls may name. ``resolvable``: a ``templateRef``
+    has been followed already and what it lacks is reported elsewhere."""
+    if "templateRef" in tmpl:
+        problems.append(f"{where}: templateRef is not supported")
+    bodies = [b for b in BODY_TYPES if b in tmpl]
+    foreign = [b for b in UNSUPPORTED_BODY_TYPES if b in tmpl]
+    if foreign:
+        problems.append(f"{where}: {foreign[0]} templates are not supported")
+    elif not bodies and "templateRef" not in tmpl:  # that one is its (refused) body
+        problems.append(
+            f"{where}: no body (expected one of {', '.join(BODY_TYPES)})"
+        )
+    if len(bodies) + len(foreign) > 1:
+        problems.append(
+            f"{where}: several bodies ({', '.join(bodies + foreign)}); expected exactly one"
+        )
+
+    if tmpl.get("parallelism") is not None and not _positive_int(tmpl["parallelism"]):
+        problems.append(f"{where}: parallelism must be a positive integer")
+
+    calls = calls_of(tmpl)
+    kind = "tasks" if "dag" in tmpl else ("steps" if "steps" in tmpl else "")
+    seen: Set[str] = set()
+    for call in calls:
+        cname = call.get("name")
+        cwhere = f"{where}: {kind[:-1]} {cname!r}"
+        if cname is None:
+            problems.append(f"{where}: a {kind[:-1]} has no name")
+        elif cname in seen:
+            problems.append(f"{cwhere} is defined more than once")
+        seen.add(cname)
+        if "templateRef" in call:
+            if call.get("template") is not None:
+                problems.append(f"{cwhere}: template and templateRef are mutually exclusive")
+            elif not well_formed_ref(call["templateRef"]):
+                problems.append(f"{cwhere}: templateRef needs a name and a template")
+            elif not resolvable:
+                problems.append(f"{cwhere}: templateRef {UNRESOLVABLE}")
+        elif call.get("template") not in local:
+            problems.append(f"{cwhere}: template {call.get('template')!r} not found")
+        for key in ("withSequence", "continueOn"):
+            if key in call:
+                problems.append(f"{cwhere}: {key} is not supported")
+        if "withItems" in call and "withParam" in call:
+            problems.append(f"{cwhere}: withItems and withParam are mutually exclusive")
+        if "withItems" in call and not isinstance(call["withItems"], list):
+            problems.append(f"{cwhere}: withItems is not a list")
+
+    if kind == "tasks":
+        deps: Dict[str, List[str]] = {}
+        for task in calls:
+            tname = task.get("name")
+            twhere = f"{where}: task {tname!r}"
+            if task.get("depends") and parse_depends(task["depends"]) is None:
+                problems.append(
+                    f"{twhere}: unsupported depends expression {task['depends']!r} "
+                    "(only task names joined by && are supported)"
+                )
+            if "dependencies" in task and not isinstance(task["dependencies"], list):
+                problems.append(f"{twhere}: dependencies is not a list")
+            deps[tname] = task_dependencies(task)
+            for d in deps[tname]:
+                if d not in seen:
+                    problems.append(f"{twhere}: depends on unknown task {d!r}")
+        cyc = _find_cycle(deps)
+        if cyc is not None:
+            problems.append(f"{where}: dependency cycle through task {cyc!r}")
+
+    inputs = _param_names((tmpl.get("inputs") or {}).get("parameters"))
+    names = {str(n) for n in seen if n is not None}
+    # the template's own fields first, then each step or task on its own:
+    # {{item}} is valid only inside one that loops
+    body = {k: v for k, v in tmpl.items() if k not in ("steps", "dag")}
+    _check_refs(where, body, inputs, wf_params, names, kind, problems)
+    for call in calls:
+        _check_refs(f"{where}: {kind[:-1]} {call.get('name')!r}", call, inputs, wf_params,
+                    names, kind, problems,
+                    in_loop="withItems" in call or "withParam" in call)
+
+
+def _named_templates(spec: Dict[str, Any], where: str,
+                     problems: List[str]) -> Dict[Any, Dict[str, Any]]:
+    templates: Dict[Any, Dict[str, Any]] = {}
+    listed = spec.get("templates") or []
+    if not isinstance(listed, list):
+        problems.append(f"spec.templates{where} is not a list")
+        return templates
+    for t in listed:
+        if not isinstance(t, dict) or not isinstance(t.get("name"), (str, int, float)):
+            problems.append(f"a template{where} has no name")
             continue
         if t["name"] in templates:
-            problems.append(f"template {t['name']!r} is defined more than once")
+            problems.append(f"template {t['name']!r}{where} is defined more than once")
         templates[t["name"]] = t
+    return templates
+
+
+def _check_shared(found: Resolved, skip: str, wf_params: Optional[Set[str]],
+                  problems: List[str]) -> None:
+    """Every shared template that was reached, in its own scope; those of
+    scope ``skip`` have been checked by the caller."""
+    for key, tmpl in found.stored.items():
+        scope = key[:key.rindex("/")]
+        if scope != skip:
+            _check_template(template_where(tmpl.get("name"), scope), tmpl,
+                            found.scopes[scope], True, wf_params, problems)
+
+
+def validate_workflow_spec(spec: Any, templates: Any = None) -> List[str]:
+    """Problems that would stop ``spec`` from running locally; ``[]`` when
+    it is clean.
+
+    ``templates`` gives the shared templates: a lookup ``(cluster_scope,
+    name) -> object or None``, or the :class:`~.templates.Resolved` bundle of
+    a spec that was resolved already. The effective whole is then checked:
+    ``workflowTemplateRef`` merged in, every reachable shared template in its
+    own scope, every ``{{workflow.parameters.X}}`` against the effective
+    arguments. A reference that does not resolve is reported alone: the rest
+    cannot be judged without it. Without ``templates`` each reference is one
+    problem that says so."""
+    if not isinstance(spec, dict):
+        return ["workflow spec is not a map"]
+    found: Optional[Resolved] = None
+    if templates is not None:
+        found = templates if isinstance(templates, Resolved) else resolve(spec, templates)
+        if found.errors:
+            return found.problems()
+        spec = found.spec
+    elif "workflowTemplateRef" in spec:
+        return [f"spec.workflowTemplateRef {UNRESOLVABLE}"]
+    problems: List[str] = []
+    own = _named_templates(spec, "", problems)
 
     entry = spec.get("entrypoint")
-    if entry not in templates:
+    if entry not in own:
         problems.append(f"entrypoint {entry!r} not found")
     on_exit = spec.get("onExit")
-    if on_exit is not None and on_exit not in templates:
+    if on_exit is not None and on_exit not in own:
         problems.append(f"onExit template {on_exit!r} not found")
 
     if spec.get("parallelism") is not None and not _positive_int(spec["parallelism"]):
@@ -184,77 +314,38 @@ def validate_workflow_spec(spec: Any) -> List[str]:
     wf_params = _param_names((spec.get("arguments") or {}).get("parameters"))
     _check_refs("spec.arguments", spec.get("arguments"), set(), wf_params, set(), "", problems)
 
-    for name, tmpl in templates.items():
-        where = f"template {name!r}"
-        if "templateRef" in tmpl:
-            problems.append(f"{where}: templateRef is not supported")
-        bodies = [b for b in BODY_TYPES if b in tmpl]
-        foreign = [b for b in UNSUPPORTED_BODY_TYPES if b in tmpl]
-        if foreign:
-            problems.append(f"{where}: {foreign[0]} templates are not supported")
-        elif not bodies:
-            problems.append(
-                f"{where}: no body (expected one of {', '.join(BODY_TYPES)})"
-            )
-        if len(bodies) + len(foreign) > 1:
-            problems.append(
-                f"{where}: several bodies ({', '.join(bodies + foreign)}); expected exactly one"
-            )
+    for name, tmpl in own.items():
+        _check_template(template_where(name), tmpl, own, found is not None,
+                        wf_params, problems)
+    if found is not None:
+        _check_shared(found, OWN_SCOPE, wf_params, problems)
+    return problems
 
-        if tmpl.get("parallelism") is not None and not _positive_int(tmpl["parallelism"]):
-            problems.append(f"{where}: parallelism must be a positive integer")
 
-        calls = _calls(tmpl)
-        kind = "tasks" if "dag" in tmpl else ("steps" if "steps" in tmpl else "")
-        seen: Set[str] = set()
-        for call in calls:
-            cname = call.get("name")
-            cwhere = f"{where}: {kind[:-1]} {cname!r}"
-            if cname is None:
-                problems.append(f"{where}: a {kind[:-1]} has no name")
-            elif cname in seen:
-                problems.append(f"{cwhere} is defined more than once")
-            seen.add(cname)
-            if "templateRef" in call:
-                problems.append(f"{cwhere}: templateRef is not supported")
-            elif call.get("template") not in templates:
-                problems.append(f"{cwhere}: template {call.get('template')!r} not found")
-            for key in ("withSequence", "continueOn"):
-                if key in call:
-                    problems.append(f"{cwhere}: {key} is not supported")
-            if "withItems" in call and "withParam" in call:
-                problems.append(f"{cwhere}: withItems and withParam are mutually exclusive")
-            if "withItems" in call and not isinstance(call["withItems"], list):
-                problems.append(f"{cwhere}: withItems is not a list")
-
-        if kind == "tasks":
-            deps: Dict[str, List[str]] = {}
-            for task in calls:
-                tname = task.get("name")
-                twhere = f"{where}: task {tname!r}"
-                if task.get("depends") and parse_depends(task["depends"]) is None:
-                    problems.append(
-                        f"{twhere}: unsupported depends expression {task['depends']!r} "
-                        "(only task names joined by && are supported)"
-                    )
-                if "dependencies" in task and not isinstance(task["dependencies"], list):
-                    problems.append(f"{twhere}: dependencies is not a list")
-                deps[tname] = task_dependencies(task)
-                for d in deps[tname]:
-                    if d not in seen:
-                        problems.append(f"{twhere}: depends on unknown task {d!r}")
-            cyc = _find_cycle(deps)
-            if cyc is not None:
-                problems.append(f"{where}: dependency cycle through task {cyc!r}")
-
-        inputs = _param_names((tmpl.get("inputs") or {}).get("parameters"))
-        names = {str(n) for n in seen if n is not None}
-        # the template's own fields first, then each step or task on its own:
-        # {{item}} is valid only inside one that loops
-        body = {k: v for k, v in tmpl.items() if k not in ("steps", "dag")}
-        _check_refs(where, body, inputs, wf_params, names, kind, problems)
-        for call in calls:
-            _check_refs(f"{where}: {kind[:-1]} {call.get('name')!r}", call, inputs, wf_params,
-                        names, kind, problems,
-                        in_loop="withItems" in call or "withParam" in call)
+def validate_template_library(obj: Any, templates: Optional[Lookup] = None) -> List[str]:
+    """Problems of one ``WorkflowTemplate`` / ``ClusterWorkflowTemplate``
+    document, checked as a library: every template it holds, in its own
+    scope. ``entrypoint`` is optional and workflow parameters need not be
+    declared, since the Workflow that uses it may bring them."""
+    if not isinstance(obj, dict) or not isinstance(obj.get("spec"), dict):
+        return ["invalid workflow template, missing spec"]
+    if not isinstance((obj.get("metadata") or {}).get("name"), str):
+        return ["invalid workflow template, missing metadata.name"]
+    spec = obj["spec"]
+    if templates is not None:
+        scope, found = resolve_library(obj, templates)
+    else:
+        scope, found = library_scope(obj), Resolved()
+    if found.errors:
+        return found.problems()
+    problems: List[str] = []
+    of = f" of {scope_label(scope)}"
+    local = _named_templates(spec, of, problems)
+    for key in ("entrypoint", "onExit"):
+        if spec.get(key) is not None and spec[key] not in local:
+            problems.append(f"{key} {spec[key]!r}{of} not found")
+    for name, tmpl in local.items():
+        _check_template(template_where(name, scope), tmpl, local, templates is not None,
+                        None, problems)
+    _check_shared(found, scope, None, problems)
     return problems
