@@ -18,29 +18,39 @@ that role in-process:
   can run health checks standalone without a cluster. The template walk
   itself lives in :mod:`.executor`, substitution and ``when`` in
   :mod:`.template`, static checks in :mod:`.validate`.
+
+Who may start, and in what order, is decided by :mod:`.admission`; the shared
+templates are kept by :mod:`.template_cache`. What is here is the life of one
+Workflow: its status writes, its timers and its tasks.
 """
 from __future__ import annotations
 
 import asyncio
-import bisect
+import functools
 import logging
 import time
+from collections import deque
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
+from ..api.types import k8s_now, parse_k8s_time
 from ..kube.client import KubeClient
 from ..kube.errors import ConflictError, NotFoundError
 from ..kube.registry import WF_API_VERSION, WF_KIND
-from .templates import CWFT_KIND, WFT_KIND, has_references, resolve
+from .admission import (  # noqa: F401 - the names were born here and stay importable
+    POSTPONED_MESSAGE,
+    QUEUE_EXPIRED_MESSAGE,
+    Admission,
+    Entry,
+    _positive,
+    _priority,
+    mutex_names,
+)
+from .template_cache import TemplateCache
+from .templates import has_references, resolve
 
 log = logging.getLogger("active_monitor_amd.workflow")
 
 Phase = str  # "Pending" | "Running" | "Succeeded" | "Failed"
-
-#: status.message of a Workflow that waits for one of the engine's slots
-POSTPONED_MESSAGE = ("Workflow processing has been postponed because too many "
-                     "workflows are already running")
-#: status.message of a Workflow whose activeDeadlineSeconds ran out in the queue
-QUEUE_EXPIRED_MESSAGE = "deadline exceeded while waiting to start"
 
 PolicyResult = Optional[Tuple[Phase, str]]
 Policy = Callable[[Dict[str, Any]], PolicyResult]
@@ -58,51 +68,43 @@ def never_complete(wf: Dict[str, Any]) -> PolicyResult:
     return None
 
 
-def _positive(name: str, value: Any) -> Optional[int]:
-    if value is None:
-        return None
-    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
-        raise ValueError(f"{name} must be a positive integer, got {value!r}")
-    return value
+def _key(wf: Dict[str, Any]) -> str:
+    meta = wf["metadata"]
+    return f'{meta.get("namespace", "")}/{meta["name"]}'
 
 
-def mutex_names(spec: Any) -> List[str]:
-    """Names under ``spec.synchronization.mutex`` and ``.mutexes``, duplicates
-    removed, order kept."""
-    sync = spec.get("synchronization") if isinstance(spec, dict) else None
-    if not isinstance(sync, dict):
-        return []
-    several = sync.get("mutexes")
-    found = [sync.get("mutex")] + (several if isinstance(several, list) else [])
-    return list(dict.fromkeys(
-        str(m["name"]) for m in found if isinstance(m, dict) and m.get("name")
-    ))
+class _Record:
+    """A Workflow the engine has taken up, from its ``ADDED`` event (or the
+    start-up list) until its run has ended, or it was deleted or has expired
+    before it ran. Each task is None before it is started.
 
+    ``found``       the spec resolved against the shared templates, if it
+                    refers to any: the snapshot that admission and the run read
+    ``entry``       its place in the admission queue, while it waits there
+    ``pending``     its one ``Pending`` write, which the next write to the
+                    same Workflow waits for
+    ``expiry``      the timer of its deadline in the queue
+    ``confirming``  the direct reads of templates the cache lacks
+    ``run``         its run
+    """
 
-def _priority(spec: Dict[str, Any]) -> int:
-    try:
-        return int(spec.get("priority") or 0)
-    except (TypeError, ValueError):
-        return 0
+    __slots__ = ("wf", "key", "found", "entry", "pending", "expiry", "confirming", "run")
 
-
-class _Queued:
-    """A Workflow that waits to be admitted. ``order`` sorts the queue:
-    higher ``spec.priority``, then earlier ``creationTimestamp``, then
-    arrival. ``postponed`` is the task of its one ``Pending`` write, which
-    the next write to the same Workflow waits for."""
-
-    __slots__ = ("wf", "key", "ns", "order", "mutexes", "postponed", "expiry")
-
-    def __init__(self, wf: Dict[str, Any], key: str, ns: str, order: Tuple[int, str, int],
-                 mutexes: List[Tuple[str, str]]):
+    def __init__(self, wf: Dict[str, Any], key: str):
         self.wf = wf
         self.key = key
-        self.ns = ns
-        self.order = order
-        self.mutexes = mutexes
-        self.postponed: Optional["asyncio.Future[Any]"] = None
+        self.found: Any = None
+        self.entry: Optional[Entry] = None
+        self.pending: Optional["asyncio.Future[Any]"] = None
         self.expiry: Optional[asyncio.TimerHandle] = None
+        self.confirming: Optional["asyncio.Future[Any]"] = None
+        self.run: Optional["asyncio.Future[Any]"] = None
+
+    @property
+    def spec(self) -> Any:
+        """The spec that admission reads: priority, mutexes, the deadline
+        that runs in the queue."""
+        return self.found.spec if self.found is not None else self.wf.get("spec")
 
 
 class _EngineBase:
@@ -139,18 +141,10 @@ class _EngineBase:
         self.namespace = namespace
         self.ttl_seconds = ttl_seconds
         self.recover = recover
-        self.parallelism = _positive("parallelism", parallelism)
-        self.namespace_parallelism = _positive("namespace_parallelism",
-                                               namespace_parallelism)
+        self._admission = Admission(parallelism, namespace_parallelism)
+        self.parallelism = self._admission.parallelism
+        self.namespace_parallelism = self._admission.namespace_parallelism
         self.max_processes = _positive("max_processes", max_processes)
-        # without a Workflow limit only a Workflow that names a mutex is queued
-        self._limited = parallelism is not None or namespace_parallelism is not None
-        self._queue: List[_Queued] = []  # sorted by .order
-        self._queued: Dict[str, _Queued] = {}
-        self._arrivals = 0
-        self._admitted = 0
-        self._admitted_ns: Dict[str, int] = {}
-        self._locked: set = set()  # (namespace, mutex name) of admitted runs
         self._stopping = False
         self.postponed_total = 0
         self.expired_in_queue = 0
@@ -161,9 +155,13 @@ class _EngineBase:
         self._recovered_rv = 0
         self._task: Optional[asyncio.Task] = None
         self._sub = None
-        self._inflight: Dict[str, asyncio.Task] = {}
-        from collections import deque
-
+        # by key: the newest Workflow of that name. A run outlives its
+        # Workflow's deletion, so the run of an earlier one may still be
+        # going; its record is reachable from its task alone.
+        self._records: Dict[str, _Record] = {}
+        #: every task started and not yet done, whatever it is for
+        self._tasks: set = set()
+        self._running = 0
         self._ttl_handles: "deque" = deque()
 
     async def start(self) -> None:
@@ -178,11 +176,11 @@ class _EngineBase:
             finished.sort(key=lambda pair: pair[0])
             for left, wf in finished:
                 self._schedule_ttl(wf, left)
-            if self._queue:
+            if len(self._admission):
                 # everything the list held is in the queue: admit in order
                 self._pump()
-                for entry in list(self._queue):
-                    self._postpone(entry)
+                for entry in self._admission:
+                    self._postpone(self._records[entry.key])
         log.info("workflow engine limits: parallelism=%s namespace_parallelism=%s "
                  "max_processes=%s", *(
                      "unlimited" if v is None else v for v in self.limits().values()))
@@ -191,9 +189,9 @@ class _EngineBase:
     async def stop(self) -> None:
         # what is queued stays Pending, for a restart over the same store
         self._stopping = True
-        for entry in self._queue:
-            if entry.expiry is not None:
-                entry.expiry.cancel()
+        for rec in self._records.values():
+            if rec.expiry is not None:
+                rec.expiry.cancel()
         if self._sub is not None:
             self._sub.close()
         if self._task is not None:
@@ -202,7 +200,7 @@ class _EngineBase:
                 await self._task
             except (asyncio.CancelledError, Exception):
                 pass
-        for t in self._inflight.values():
+        for t in self._tasks:
             t.cancel()
         for h in self._ttl_handles:
             h.cancel()
@@ -214,8 +212,6 @@ class _EngineBase:
             if self._recovered and self._taken_at_start(ev["type"], wf):
                 continue
             if ev["type"] == "DELETED":
-                if self._queued:
-                    self._dequeue(wf)
                 self._deleted(wf)
             if ev["type"] != "ADDED":
                 continue
@@ -238,24 +234,38 @@ class _EngineBase:
         return ev_type == "ADDED" and meta.get("uid") in self._recovered
 
     def _deleted(self, wf: Dict[str, Any]) -> None:
-        """The Workflow is gone: TTL, owner cascade or a user's delete."""
+        """The Workflow is gone: TTL, owner cascade or a user's delete. One
+        that has not started never runs; a run goes on until it ends."""
+        rec = self._records.get(_key(wf))
+        if rec is None or rec.run is not None:
+            return
+        del self._records[rec.key]
+        if rec.entry is not None:
+            self._admission.remove(rec.key)
+            rec.entry = None
+        if rec.expiry is not None:
+            rec.expiry.cancel()
+        if rec.confirming is not None:
+            rec.confirming.cancel()  # not taken up: there is nothing to run any more
 
-    def _spawn(self, wf: Dict[str, Any], coro: Any, prefix: str = "") -> "asyncio.Future[Any]":
-        """``prefix`` keeps a side task (``pending:``, ``expired:``) apart
-        from the run of the same Workflow."""
-        key = f'{prefix}{(wf["metadata"].get("namespace", ""))}/{wf["metadata"]["name"]}'
+    def _spawn(self, coro: Any, run_of: Optional[_Record] = None) -> "asyncio.Future[Any]":
+        """Every task starts here. ``run_of``: the task is that record's run."""
         task = asyncio.ensure_future(coro)
-        self._inflight[key] = task
-
-        def done(t: "asyncio.Future[Any]", k: str = key) -> None:
-            # a later task may have taken the key: that one stays
-            if self._inflight.get(k) is t:
-                del self._inflight[k]
-
-        task.add_done_callback(done)
+        self._tasks.add(task)
+        if run_of is None:
+            task.add_done_callback(self._tasks.discard)
+        else:
+            self._running += 1
+            run_of.run = task
+            task.add_done_callback(functools.partial(self._ended, run_of))
         return task
 
-    # -- admission --------------------------------------------------------
+    def _ended(self, rec: _Record, run: Any) -> None:
+        self._tasks.discard(run)
+        self._running -= 1
+        # a Workflow created since under the same name has a record of its own
+        if self._records.get(rec.key) is rec:
+            del self._records[rec.key]
 
     def limits(self) -> Dict[str, Optional[int]]:
         return {"parallelism": self.parallelism,
@@ -266,8 +276,8 @@ class _EngineBase:
         """Counters for ``/statusz``. ``running`` counts the runs in flight,
         admitted or never queued; ``processes`` the leaf processes alive."""
         return {
-            "running": sum(1 for key in self._inflight if ":" not in key),
-            "queued": len(self._queue),
+            "running": self._running,
+            "queued": len(self._admission),
             "postponed_total": self.postponed_total,
             "expired_in_queue": self.expired_in_queue,
             "processes": self._processes(),
@@ -277,142 +287,96 @@ class _EngineBase:
     def _processes(self) -> int:
         return 0
 
+    # -- one Workflow, from its ADDED event to the end of its run ------------
+
     def _submit(self, wf: Dict[str, Any], recovering: bool = False) -> None:
-        """Run ``wf`` now, or queue it when a limit or a mutex may stand in
-        its way. ``recovering``: only queue it, start() admits once all that
-        it found is queued."""
-        spec = self._spec_of(wf)
-        names = mutex_names(spec) if isinstance(spec, dict) and "synchronization" in spec else None
-        if not self._limited and not names:
-            self._spawn(wf, self._run(wf))
-            return
-        meta = wf["metadata"]
-        ns = meta.get("namespace", "")
-        key = f'{ns}/{meta["name"]}'
-        if key in self._queued:
-            return
-        self._arrivals += 1
-        order = (-_priority(spec if isinstance(spec, dict) else {}),
-                 str(meta.get("creationTimestamp") or ""), self._arrivals)
-        entry = _Queued(wf, key, ns, order, [(ns, n) for n in names or ()])
-        bisect.insort(self._queue, entry, key=lambda e: e.order)
-        self._queued[key] = entry
-        if not recovering:
+        """``recovering``: only queue it, start() admits once all that it
+        found is queued."""
+        key = _key(wf)
+        have = self._records.get(key)
+        if have is not None and have.run is None:
+            return  # queued already, or its templates are being read
+        rec = self._records[key] = _Record(wf, key)
+        self._take_up(rec, recovering)
+
+    def _take_up(self, rec: _Record, recovering: bool = False) -> None:
+        """Run ``rec`` now, or queue it when a limit or a mutex may stand in
+        its way."""
+        meta = rec.wf["metadata"]
+        rec.entry = self._admission.offer(rec.key, meta.get("namespace", ""), rec.spec,
+                                          meta.get("creationTimestamp"))
+        if rec.entry is None:
+            self._spawn(self._run(rec), rec)
+        elif not recovering:
             self._pump()
-            if key in self._queued:
-                self._postpone(entry)
-
-    def _spec_of(self, wf: Dict[str, Any]) -> Any:
-        """The spec that admission reads: priority, mutexes, the deadline
-        that runs in the queue."""
-        return wf.get("spec")
-
-    def _blocked_by(self, entry: _Queued) -> Optional[str]:
-        """The ``Pending`` message for what keeps ``entry`` from starting
-        now, None when nothing does."""
-        if self.parallelism is not None and self._admitted >= self.parallelism:
-            return POSTPONED_MESSAGE
-        if (self.namespace_parallelism is not None
-                and self._admitted_ns.get(entry.ns, 0) >= self.namespace_parallelism):
-            return POSTPONED_MESSAGE
-        for ns, name in entry.mutexes:
-            if (ns, name) in self._locked:
-                return f"Waiting for {ns}/Mutex/{name} lock"
-        return None
+            if rec.entry is not None:
+                self._postpone(rec)
 
     def _pump(self) -> None:
-        """Admit, in queue order, every Workflow that can start. One that
-        waits for its namespace or for a mutex is passed over."""
+        """Start every Workflow that admission lets through."""
         if self._stopping:
             return
-        i = 0
-        while i < len(self._queue):
-            if self.parallelism is not None and self._admitted >= self.parallelism:
-                break
-            entry = self._queue[i]
-            if self._blocked_by(entry) is not None:
-                i += 1
-                continue
-            del self._queue[i]
-            del self._queued[entry.key]
-            if entry.expiry is not None:
-                entry.expiry.cancel()
-            # the slot and the mutexes are taken here, all or none, before
-            # the next entry is looked at
-            self._admitted += 1
-            self._admitted_ns[entry.ns] = self._admitted_ns.get(entry.ns, 0) + 1
-            self._locked.update(entry.mutexes)
-            self._spawn(entry.wf, self._run_admitted(entry))
+        for entry in self._admission.admit():
+            rec = self._records[entry.key]
+            rec.entry = None
+            if rec.expiry is not None:
+                rec.expiry.cancel()
+            self._spawn(self._run_admitted(rec, entry), rec)
 
-    async def _run_admitted(self, entry: _Queued) -> None:
+    async def _run_admitted(self, rec: _Record, entry: Entry) -> None:
         try:
-            if entry.postponed is not None:
-                await asyncio.wait([entry.postponed])  # Pending lands before Running
-            await self._run(entry.wf)
+            if rec.pending is not None:
+                await asyncio.wait([rec.pending])  # Pending lands before Running
+            await self._run(rec)
         finally:
-            self._admitted -= 1
-            left = self._admitted_ns[entry.ns] - 1
-            if left:
-                self._admitted_ns[entry.ns] = left
-            else:
-                del self._admitted_ns[entry.ns]
-            self._locked.difference_update(entry.mutexes)
+            self._admission.release(entry)
             self._pump()
 
-    def _postpone(self, entry: _Queued) -> None:
-        """``entry`` stays in the queue: write ``Pending`` once and start
-        the clock of its deadline."""
+    def _postpone(self, rec: _Record) -> None:
+        """``rec`` stays in the queue: write ``Pending`` once and start the
+        clock of its deadline."""
         self.postponed_total += 1
-        wf = entry.wf
+        wf = rec.wf
         if (wf.get("status") or {}).get("phase") != "Pending":  # else: recovered
-            message = self._blocked_by(entry) or POSTPONED_MESSAGE
-            entry.postponed = self._spawn(
-                wf, self._set_status(wf, {"phase": "Pending", "message": message}),
-                "pending:")
-        spec = self._spec_of(wf)
+            message = self._admission.blocked_by(rec.entry) or POSTPONED_MESSAGE
+            rec.pending = self._spawn(
+                self._set_status(wf, {"phase": "Pending", "message": message}))
+        spec = rec.spec
         deadline = spec.get("activeDeadlineSeconds") if isinstance(spec, dict) else None
         try:
             deadline = float(deadline) if deadline and deadline is not True else 0.0
         except (TypeError, ValueError):
             deadline = 0.0
         if deadline > 0:
-            entry.expiry = asyncio.get_event_loop().call_later(
-                deadline, self._expire, entry)
+            rec.expiry = asyncio.get_event_loop().call_later(deadline, self._expire, rec)
 
-    def _expire(self, entry: _Queued) -> None:
-        if self._queued.get(entry.key) is not entry:
+    def _expire(self, rec: _Record) -> None:
+        if rec.entry is None:
             return
-        del self._queued[entry.key]
-        self._queue.remove(entry)
+        self._admission.remove(rec.key)
+        rec.entry = None
+        del self._records[rec.key]
         self.expired_in_queue += 1
         log.warning("workflow %s waited out its activeDeadlineSeconds in the "
-                    "queue: failing it", entry.key)
-        self._spawn(entry.wf, self._fail_expired(entry), "expired:")
+                    "queue: failing it", rec.key)
+        self._spawn(self._fail_expired(rec))
 
-    async def _fail_expired(self, entry: _Queued) -> None:
-        if entry.postponed is not None:
-            await asyncio.wait([entry.postponed])
-        await self._set_status(entry.wf, {
-            "phase": "Failed", "finishedAt": _now_iso(), "message": QUEUE_EXPIRED_MESSAGE,
+    async def _fail_expired(self, rec: _Record) -> None:
+        if rec.pending is not None:
+            await asyncio.wait([rec.pending])
+        await self._set_status(rec.wf, {
+            "phase": "Failed", "finishedAt": k8s_now(), "message": QUEUE_EXPIRED_MESSAGE,
         })
-        self._schedule_ttl(entry.wf)
-
-    def _dequeue(self, wf: Dict[str, Any]) -> None:
-        """A DELETED Workflow leaves the queue; it never runs."""
-        meta = wf["metadata"]
-        entry = self._queued.pop(f'{meta.get("namespace", "")}/{meta["name"]}', None)
-        if entry is not None:
-            self._queue.remove(entry)
-            if entry.expiry is not None:
-                entry.expiry.cancel()
+        self._schedule_ttl(rec.wf)
 
     def _recover(self, wf: Dict[str, Any], finished: List[Any]) -> None:
         """Handle one Workflow found at start by the state it is in; a
         terminal one is appended to ``finished`` as ``(ttl left, wf)`` for
         the caller to schedule."""
         meta = wf["metadata"]
-        key = f'{meta.get("namespace", "")}/{meta["name"]}'
-        if key in self._inflight:
+        key = _key(wf)
+        rec = self._records.get(key)
+        if rec is not None and rec.run is not None:
             return
         status = wf.get("status") or {}
         phase = status.get("phase")
@@ -435,13 +399,11 @@ class _EngineBase:
         else:
             log.warning("workflow %s was running when the engine stopped: "
                         "failing it", key)
-            self._spawn(wf, self._fail_interrupted(wf))
+            self._spawn(self._fail_interrupted(wf))
 
     def _ttl_left(self, finished_at: Any) -> float:
         """``ttl_seconds`` less the time since ``finishedAt``, floored at 0;
         a missing or unparsable ``finishedAt`` counts from now."""
-        from ..api.types import parse_k8s_time
-
         try:
             finished = parse_k8s_time(finished_at)
         except (TypeError, ValueError):
@@ -453,12 +415,12 @@ class _EngineBase:
 
     async def _fail_interrupted(self, wf: Dict[str, Any]) -> None:
         status = dict(wf.get("status") or {})
-        status.update(phase="Failed", finishedAt=_now_iso(),
+        status.update(phase="Failed", finishedAt=k8s_now(),
                       message=self.INTERRUPTED_MESSAGE)
         await self._set_status(wf, status)
         self._schedule_ttl(wf)
 
-    async def _run(self, wf: Dict[str, Any]) -> None:  # pragma: no cover - abstract
+    async def _run(self, rec: _Record) -> None:  # pragma: no cover - abstract
         raise NotImplementedError
 
     def _schedule_ttl(self, wf: Dict[str, Any], delay: Optional[float] = None) -> None:
@@ -467,23 +429,10 @@ class _EngineBase:
         if delay is None:
             delay = self.ttl_seconds
         meta = wf["metadata"]
-        ns, name = meta.get("namespace", ""), meta["name"]
-
-        def _gc() -> None:
-            async def delete() -> None:
-                try:
-                    await self.client.delete(WF_API_VERSION, WF_KIND, ns, name)
-                except Exception:
-                    pass
-
-            task = asyncio.ensure_future(delete())
-            self._inflight[f"ttl:{ns}/{name}"] = task
-            task.add_done_callback(
-                lambda t: self._inflight.pop(f"ttl:{ns}/{name}", None)
-            )
-
         loop = asyncio.get_event_loop()
-        self._ttl_handles.append(loop.call_later(delay, _gc))
+        # no closure here: whatever the timer holds lives as long as the TTL
+        self._ttl_handles.append(loop.call_later(
+            delay, self._ttl_over, meta.get("namespace", ""), meta["name"]))
         # handles are appended in firing order (constant ttl; start() arms
         # the remaining TTLs of recovered workflows first, shortest first,
         # and none exceeds ttl): drop spent ones from the front — O(1)
@@ -493,6 +442,15 @@ class _EngineBase:
             self._ttl_handles[0].cancelled() or self._ttl_handles[0].when() <= now
         ):
             self._ttl_handles.popleft()
+
+    def _ttl_over(self, ns: str, name: str) -> None:
+        self._spawn(self._delete(ns, name))
+
+    async def _delete(self, ns: str, name: str) -> None:
+        try:
+            await self.client.delete(WF_API_VERSION, WF_KIND, ns, name)
+        except Exception:
+            pass
 
     async def _set_status(self, wf: Dict[str, Any], status: Dict[str, Any]) -> bool:
         """Write the Workflow status the way the Argo controller does (the
@@ -534,17 +492,18 @@ class ScriptedWorkflowEngine(_EngineBase):
         self.delay = delay
         self.completed = 0
 
-    async def _run(self, wf: Dict[str, Any]) -> None:
+    async def _run(self, rec: _Record) -> None:
+        wf = rec.wf
         decision = self.policy(wf)
         if decision is None:
             return  # leave pending: the controller's IEB timeout takes over
         if self.delay > 0:
             # instant completions skip the intermediate Running write — one
             # status update (and one spurious watcher wakeup) less per run
-            await self._set_status(wf, {"phase": "Running", "startedAt": _now_iso()})
+            await self._set_status(wf, {"phase": "Running", "startedAt": k8s_now()})
             await asyncio.sleep(self.delay)
         phase, message = decision[0], decision[1]
-        status: Dict[str, Any] = {"phase": phase, "finishedAt": _now_iso()}
+        status: Dict[str, Any] = {"phase": phase, "finishedAt": k8s_now()}
         if message:
             status["message"] = message
         if len(decision) > 2 and decision[2]:  # type: ignore[misc]
@@ -552,12 +511,6 @@ class ScriptedWorkflowEngine(_EngineBase):
         await self._set_status(wf, status)
         self._schedule_ttl(wf)
         self.completed += 1
-
-
-def _now_iso() -> str:
-    from ..api.types import k8s_now
-
-    return k8s_now()
 
 
 class LocalWorkflowEngine(_EngineBase):
@@ -586,7 +539,7 @@ class LocalWorkflowEngine(_EngineBase):
     - shared templates: ``templateRef`` on steps and tasks and
       ``spec.workflowTemplateRef``, resolved once per Workflow from a
       watch-fed cache of WorkflowTemplates and ClusterWorkflowTemplates, before
-      admission reads the spec (:mod:`.templates`);
+      admission reads the spec (:mod:`.templates`, :mod:`.template_cache`);
     - workflow-level ``activeDeadlineSeconds``. Every leaf runs in its own
       process group, which is killed when the deadline passes or the engine
       stops.
@@ -613,99 +566,52 @@ class LocalWorkflowEngine(_EngineBase):
         #: a :class:`~.logs.LogStore` for what the leaves print, or None;
         #: whoever built it closes it
         self.logs = logs
-        # shared templates, fed by a watch per kind: (cluster scope,
-        # namespace or "", name) → object. Objects are replaced, never
-        # changed in place, so a run keeps what it resolved against.
-        self._templates: Dict[Tuple[bool, str, str], Dict[str, Any]] = {}
-        self._template_subs: List[Any] = []
-        self._template_tasks: List["asyncio.Future[Any]"] = []
-        #: what :meth:`_submit` resolved, until :meth:`_run` takes it
-        self._resolved: Dict[str, Any] = {}
-        #: direct reads made for a name the cache did not have
-        self.template_reads = 0
+        self._templates = TemplateCache(client, namespace)
 
     async def start(self) -> None:
-        # the cache is whole before the first Workflow is looked at; watch
-        # first, then list, so that nothing created in between is missed
-        for kind, namespace in ((WFT_KIND, self.namespace), (CWFT_KIND, None)):
-            sub = self.client.watch(WF_API_VERSION, kind, namespace)
-            self._template_subs.append(sub)
-            for obj in await self.client.list(WF_API_VERSION, kind, namespace):
-                self._cache_template(obj)
-            self._template_tasks.append(asyncio.ensure_future(self._follow_templates(sub)))
+        # the cache is whole before the first Workflow is looked at
+        await self._templates.start()
         await super().start()
 
-    @staticmethod
-    def _template_key(obj: Dict[str, Any]) -> Tuple[bool, str, str]:
-        meta = obj.get("metadata") or {}
-        cluster = obj.get("kind") == CWFT_KIND
-        return cluster, "" if cluster else meta.get("namespace", ""), meta.get("name", "")
-
-    def _cache_template(self, obj: Dict[str, Any]) -> None:
-        """Keep ``obj`` unless what is cached is newer (a direct read and
-        the watch may deliver the same object in either order)."""
-        key = self._template_key(obj)
-        have = self._templates.get(key)
-        if have is not None:
-            try:
-                if (int(have["metadata"]["resourceVersion"])
-                        > int(obj["metadata"]["resourceVersion"])):
-                    return
-            except (KeyError, TypeError, ValueError):
-                pass  # opaque resourceVersion: the later arrival stands
-        self._templates[key] = obj
-
-    async def _follow_templates(self, sub: Any) -> None:
-        async for ev in sub:
-            if ev["type"] == "DELETED":
-                self._templates.pop(self._template_key(ev["object"]), None)
-            elif ev["type"] in ("ADDED", "MODIFIED"):
-                self._cache_template(ev["object"])
-
-    def _resolve(self, wf: Dict[str, Any]) -> Any:
-        """``wf``'s spec resolved against the cache; namespaced names are
-        looked up in the Workflow's namespace."""
-        ns = wf["metadata"].get("namespace", "")
-        return resolve(wf["spec"], lambda cluster, name: self._templates.get(
-            (cluster, "" if cluster else ns, name)))
+    @property
+    def template_reads(self) -> int:
+        """Direct reads made for a name the cache did not have."""
+        return self._templates.reads
 
     def cached_templates(self) -> List[str]:
         """What the cache holds, sorted: ``namespaced/NAMESPACE/NAME`` and
         ``cluster/NAME``."""
-        return sorted(f"cluster/{name}" if cluster else f"namespaced/{ns}/{name}"
-                      for cluster, ns, name in self._templates)
+        return self._templates.names()
 
     def cached_template(self, name: str, namespace: str = "",
                         cluster: bool = False) -> Optional[Dict[str, Any]]:
         """The cached object of that name, None when there is none; read-only."""
-        return self._templates.get((cluster, "" if cluster else namespace, name))
+        return self._templates.get(name, namespace, cluster)
 
-    def _submit(self, wf: Dict[str, Any], recovering: bool = False) -> None:
+    def _take_up(self, rec: _Record, recovering: bool = False) -> None:
         # this runs in the watch loop: whatever one Workflow's spec holds,
         # the Workflows after it are still looked at
+        wf = rec.wf
         try:
-            found = self._resolve(wf) if has_references(wf.get("spec")) else None
+            found = resolve(wf["spec"], self._templates.lookup(
+                wf["metadata"].get("namespace", ""))) if has_references(wf.get("spec")) else None
         except Exception:
             log.exception("workflow %s/%s: references not resolved, taken as it is",
                           wf["metadata"].get("namespace", ""), wf["metadata"].get("name"))
             found = None
-        if found is None:
-            super()._submit(wf, recovering)
-            return
-        if found.missing:
-            self._spawn(wf, self._confirm_missing(wf, found), "resolve:")
-            return
-        self._take_up(wf, found, recovering)
-
-    def _take_up(self, wf: Dict[str, Any], found: Any, recovering: bool = False) -> None:
-        meta = wf["metadata"]
-        self._resolved[f'{meta.get("namespace", "")}/{meta["name"]}'] = found
-        if found.errors:
-            self._spawn(wf, self._run(wf))  # fails at once: nothing to wait for
+        if found is not None and found.missing:
+            rec.confirming = self._spawn(self._confirm_missing(rec, found))
         else:
-            super()._submit(wf, recovering)
+            self._take_up_resolved(rec, found, recovering)
 
-    async def _confirm_missing(self, wf: Dict[str, Any], found: Any) -> None:
+    def _take_up_resolved(self, rec: _Record, found: Any, recovering: bool = False) -> None:
+        rec.found = found
+        if found is not None and found.errors:
+            self._spawn(self._run(rec), rec)  # fails at once: nothing to wait for
+        else:
+            super()._take_up(rec, recovering)
+
+    async def _confirm_missing(self, rec: _Record, found: Any) -> None:
         """A name the cache lacks is read once from the apiserver before the
         Workflow is failed for it: a template applied in the same instant as
         its user may not have come down the watch yet. The task is cancelled
@@ -715,70 +621,38 @@ class LocalWorkflowEngine(_EngineBase):
         when its reads are done, not in the ordered pass over what start()
         found; the cache was primed by a list just before, so this takes a
         template created in that very moment."""
-        ns = wf["metadata"].get("namespace", "")
-        asked: set = set()
-        while True:
-            wanted = [m for m in found.missing if m not in asked]
-            if not wanted:
-                break
-            for cluster, name in wanted:
-                asked.add((cluster, name))
-                self.template_reads += 1
-                try:
-                    self._cache_template(await self.client.get(
-                        WF_API_VERSION, CWFT_KIND if cluster else WFT_KIND,
-                        "" if cluster else ns, name))
-                except NotFoundError:
-                    pass
-            found = self._resolve(wf)
+        wf = rec.wf
+        found = await self._templates.read_missing(
+            wf["spec"], wf["metadata"].get("namespace", ""), found)
+        rec.confirming = None
         if not self._stopping:
-            self._take_up(wf, found)
-
-    def _spec_of(self, wf: Dict[str, Any]) -> Any:
-        meta = wf["metadata"]
-        found = self._resolved.get(f'{meta.get("namespace", "")}/{meta["name"]}')
-        return found.spec if found is not None else wf.get("spec")
+            self._take_up_resolved(rec, found)
 
     def _processes(self) -> int:
         return self.process_slots.held
 
     def _deleted(self, wf: Dict[str, Any]) -> None:
-        meta = wf["metadata"]
-        key = f'{meta.get("namespace", "")}/{meta["name"]}'
-        self._resolved.pop(key, None)
-        confirming = self._inflight.get(f"resolve:{key}")
-        if confirming is not None:
-            confirming.cancel()  # not taken up: there is nothing to run any more
+        super()._deleted(wf)
         if self.logs is not None:
-            self.logs.discard(meta.get("namespace", ""), meta["name"])
-
-    async def _fail_expired(self, entry: _Queued) -> None:
-        self._resolved.pop(entry.key, None)
-        await super()._fail_expired(entry)
+            self.logs.discard(wf["metadata"].get("namespace", ""), wf["metadata"]["name"])
 
     async def stop(self) -> None:
-        inflight = list(self._inflight.values())
-        for sub in self._template_subs:
-            sub.close()
-        for task in self._template_tasks:
-            task.cancel()
-        await asyncio.gather(*self._template_tasks, return_exceptions=True)
-        self._template_subs, self._template_tasks = [], []
+        await self._templates.stop()
         await super().stop()
         # cancelled runs kill and reap their process groups before they end
-        if inflight:
-            await asyncio.gather(*inflight, return_exceptions=True)
+        await asyncio.gather(*self._tasks, return_exceptions=True)
 
-    async def _run(self, wf: Dict[str, Any]) -> None:
+    async def _run(self, rec: _Record) -> None:
         from .executor import WorkflowRun
         from .validate import ignored_synchronization, validate_workflow_spec
 
+        wf = rec.wf
         meta = wf["metadata"]
         ns, name = meta.get("namespace", ""), meta["name"]
         # resolved once, when the Workflow was taken up: the run reads this
         # snapshot, whatever happens to the shared templates meanwhile
-        found = self._resolved.pop(f"{ns}/{name}", None)
-        spec = (found.spec if found is not None else wf.get("spec")) or {}
+        found = rec.found
+        spec = rec.spec or {}
         recorded: Dict[str, Any] = {}
         if found is not None and not found.errors:
             if found.stored_spec is not None:
@@ -792,7 +666,7 @@ class LocalWorkflowEngine(_EngineBase):
             except (OSError, ValueError) as e:
                 log.warning("no logs kept for workflow %s/%s: %s", ns, name, e)
                 logs = None
-        await self._set_status(wf, {"phase": "Running", "startedAt": _now_iso(), **recorded})
+        await self._set_status(wf, {"phase": "Running", "startedAt": k8s_now(), **recorded})
         nodes: Dict[str, Any] = {}
         outputs: List[Dict[str, Any]] = []
         if found is not None and found.errors:
@@ -818,7 +692,7 @@ class LocalWorkflowEngine(_EngineBase):
             nodes = run.nodes
             if not timed_out:  # a run that was cut short publishes no outputs
                 outputs = run.global_outputs
-        status: Dict[str, Any] = {"phase": phase, "finishedAt": _now_iso(), **recorded}
+        status: Dict[str, Any] = {"phase": phase, "finishedAt": k8s_now(), **recorded}
         if message:
             status["message"] = message
         if outputs:

@@ -17,6 +17,7 @@ import tempfile
 import time
 from typing import Any, Awaitable, Dict, List, Optional, Tuple
 
+from ..api.types import k8s_now
 from .template import (
     TemplateError,
     UnresolvedReference,
@@ -61,12 +62,6 @@ Result = Tuple[str, str, Optional[Outputs]]
 #: the template a call names: (scope, template name, the ``templateRef`` its
 #: node shows or None for a ``template:`` call); scopes as in :mod:`.templates`
 Target = Tuple[str, Any, Optional[Dict[str, Any]]]
-
-
-def _now_iso() -> str:
-    from ..api.types import k8s_now
-
-    return k8s_now()
 
 
 class Bound:
@@ -171,7 +166,7 @@ class WorkflowRun:
         nodes that were cut short."""
         for proc in list(self._procs.values()):
             _kill_group(proc)
-        now = _now_iso()
+        now = k8s_now()
         for node in self.nodes.values():
             if "phase" not in node:
                 node.update(phase="Failed", message=reason, finishedAt=now)
@@ -191,7 +186,7 @@ class WorkflowRun:
               parent: Optional[str]) -> Dict[str, Any]:
         node: Dict[str, Any] = {
             "id": node_id, "displayName": display, "type": type_,
-            "startedAt": _now_iso(), "children": [],
+            "startedAt": k8s_now(), "children": [],
         }
         if target is not None:
             tscope, template, ref = target
@@ -211,7 +206,7 @@ class WorkflowRun:
                outputs: Optional[Outputs] = None) -> None:
         node["phase"] = phase
         node["message"] = message
-        node["finishedAt"] = _now_iso()
+        node["finishedAt"] = k8s_now()
         if outputs:
             shown: Dict[str, Any] = {}
             if outputs.get("result") is not None:

@@ -417,7 +417,7 @@ def test_a_workflow_deleted_while_its_template_is_read_never_runs(run, tmp_path)
             await asyncio.wait_for(client.reading.wait(), 5)
             await client.delete(*WF, "health", "doomed")
             for _ in range(500):  # until the engine has seen the deletion
-                if not any(key.startswith("resolve:") for key in engine._inflight):
+                if not any(rec.confirming for rec in engine._records.values()):
                     break
                 await asyncio.sleep(0.01)
             client.release.set()

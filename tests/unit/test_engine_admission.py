@@ -352,7 +352,36 @@ def test_stop_leaves_the_queue_pending_and_kills_what_runs(run, tmp_path):
         assert "startedAt" not in await s.status("q1")
         assert await s.phase("running") == "Running"  # as today: killed, not finished
         assert s.engine.stats()["queued"] == 2
-        assert not s.engine._inflight
+        assert not s.engine._tasks
         assert started(tmp_path) == ["running"]
+
+    run(go(), timeout=30)
+
+
+def test_stop_kills_the_run_of_a_workflow_whose_name_was_created_again(run, tmp_path):
+    finished = tmp_path / "finished"
+    script = (f"echo x >> {tmp_path}/started; "
+              f"while [ ! -e {tmp_path}/release.x ]; do sleep 0.02; done; "
+              f"echo x >> {finished}")
+    wf = workflow(tmp_path, "x")
+    wf["spec"]["templates"][0]["container"]["command"] = ["sh", "-c", script]
+
+    async def go():
+        s = Stack(tmp_path)
+        await s.engine.start()
+        try:
+            await s.client.create(wf)
+            await until(lambda: started(tmp_path) == ["x"], "the first run")
+            await s.client.delete(*WF, "a", "x")
+            await s.client.create(wf)
+            await until(lambda: started(tmp_path) == ["x", "x"], "the second run")
+            # both runs are in flight, the first one's Workflow is gone
+            assert s.engine.stats()["running"] == 2
+        finally:
+            await s.engine.stop()
+        assert not s.engine._tasks
+        release(tmp_path, "x")
+        await asyncio.sleep(0.5)
+        assert not finished.exists()
 
     run(go(), timeout=30)
