@@ -23,7 +23,9 @@
     ``--templates`` are put into that store first. For a HealthCheck the
     check workflow runs (``--remedy``: the remedy workflow). ``--logs`` adds
     what every leaf printed, stdout and stderr, under a ``--- NODE ---`` line
-    each. Exit status 0 for ``Succeeded``, 1 for ``Failed``.
+    each; for an ``http`` leaf that is its request line, the response's
+    status line and the body that was kept. Exit status 0 for ``Succeeded``,
+    1 for ``Failed``.
 
 ``next (FILE | --cron SPEC) [-n N] [--from RFC3339] [--time-zone ZONE]``
     Print the next N (default 5) activations of a cron schedule, one per
@@ -244,13 +246,14 @@ async def _execute_with_logs(spec: Dict[str, Any], name: str,
                              templates: Optional[Templates] = None
                              ) -> Tuple[Dict[str, Any], bytes]:
     """``_execute`` over a temporary log store; also returns the log of
-    every Pod node, in start order, under a ``--- displayName ---`` line."""
+    every Pod and HTTP node, in start order, under a ``--- displayName ---``
+    line."""
     logs = LogStore()
     try:
         status = await _execute(spec, name, logs, templates)
         out: List[bytes] = []
         for node in (status.get("nodes") or {}).values():
-            if node.get("type") != "Pod" or not logs.has_run("local", name):
+            if node.get("type") not in ("Pod", "HTTP") or not logs.has_run("local", name):
                 continue
             out.append(f"--- {node['displayName']} ---\n".encode())
             try:

@@ -514,7 +514,8 @@ class ScriptedWorkflowEngine(_EngineBase):
 
 
 class LocalWorkflowEngine(_EngineBase):
-    """Executes Argo-shaped workflows locally, one subprocess per leaf.
+    """Executes Argo-shaped workflows locally: one subprocess per container
+    or script leaf, one socket per ``http`` leaf.
 
     Supported surface (docs/OPERATIONS.md has the full list and what is
     deliberately absent):
@@ -522,6 +523,10 @@ class LocalWorkflowEngine(_EngineBase):
     - ``container`` (command+args run as a local process; ``image`` is
       informational without a container runtime) and ``script`` (source piped
       to the interpreter) leaves, with ``env`` name/value pairs; ``suspend``;
+    - ``http`` leaves: one request sent from the event loop itself, without
+      a process (:mod:`.httpprobe`), judged by its status or by a
+      ``successCondition`` (:mod:`.expr`); at most ``HTTP_MAX_IN_FLIGHT``
+      over all runs, and none of them counts against ``max_processes``;
     - ``steps`` (sequential groups of parallel steps) and ``dag`` templates
       (``dependencies`` / ``depends: "a && b"``, fail-fast by default);
     - ``withItems`` / ``withParam`` fan-out and ``when`` conditions on steps
@@ -558,11 +563,14 @@ class LocalWorkflowEngine(_EngineBase):
                  max_processes: Optional[int] = None):
         super().__init__(client, namespace, ttl_seconds, recover, parallelism,
                          namespace_parallelism, max_processes)
-        from .executor import Bound
+        from .executor import HTTP_MAX_IN_FLIGHT, Bound
 
         self.completed = 0
         #: the leaf processes of all runs; holds at most ``max_processes``
         self.process_slots = Bound(self.max_processes)
+        #: the HTTP probes of all runs; they are no processes and are not
+        #: counted in :meth:`stats`
+        self.http_slots = Bound(HTTP_MAX_IN_FLIGHT)
         #: a :class:`~.logs.LogStore` for what the leaves print, or None;
         #: whoever built it closes it
         self.logs = logs
@@ -681,7 +689,8 @@ class LocalWorkflowEngine(_EngineBase):
                 log.warning("workflow %s/%s: %s not supported and ignored",
                             ns, name, " and ".join(ignored))
             run = WorkflowRun(spec, name, ns, logs=logs, process_slots=self.process_slots,
-                              templates=found.scopes if found is not None else None)
+                              templates=found.scopes if found is not None else None,
+                              http_slots=self.http_slots)
             try:
                 phase, message, timed_out = await self._run_phases(run, spec)
             except asyncio.CancelledError:

@@ -18,6 +18,9 @@ import time
 from typing import Any, Awaitable, Dict, List, Optional, Tuple
 
 from ..api.types import k8s_now
+from .expr import ExprError
+from .expr import parse as parse_expr
+from .expr import render as render_expr
 from .template import (
     TemplateError,
     UnresolvedReference,
@@ -31,7 +34,7 @@ from .template import (
     to_str,
 )
 from .templates import OWN_SCOPE, scope_key, shown_ref
-from .validate import task_dependencies
+from .validate import HTTP_DEFAULT_TIMEOUT_SECONDS, task_dependencies
 
 #: ``outputs.result`` keeps at most this many bytes of a leaf's stdout
 RESULT_MAX_BYTES = 64 * 1024
@@ -52,6 +55,8 @@ _KILL_DRAIN_SECONDS = 1.0
 #: in the process table until then; the kill path waits this long for the
 #: group to be empty, so that a workflow reported Failed has left nothing
 _KILL_REAP_SECONDS = 5.0
+#: HTTP probes in flight at once, over all runs of an engine
+HTTP_MAX_IN_FLIGHT = 64
 
 log = logging.getLogger("active_monitor_amd.workflow")
 
@@ -119,10 +124,14 @@ def _parallelism_bound(tmpl: Dict[str, Any]) -> Optional[Bound]:
 class WorkflowRun:
     def __init__(self, spec: Dict[str, Any], name: str, namespace: str,
                  logs: Any = None, process_slots: Optional[Bound] = None,
-                 templates: Optional[Dict[str, Dict[Any, Dict[str, Any]]]] = None):
+                 templates: Optional[Dict[str, Dict[Any, Dict[str, Any]]]] = None,
+                 http_slots: Optional[Bound] = None):
         """``spec`` is the effective spec; ``templates`` the shared templates
         it reaches, by scope (:attr:`.templates.Resolved.scopes`)."""
         self.spec = spec
+        #: an HTTP probe holds one slot of this, the engine's bound over the
+        #: probes of all runs, and none of ``_process_bounds``: it is no process
+        self._http_slots = http_slots
         # a leaf process holds one slot of each, taken in this order:
         # spec.parallelism, then the engine's bound over all of its runs
         self._process_bounds = [
@@ -298,6 +307,8 @@ class WorkflowRun:
             type_ = "DAG"
         elif "suspend" in tmpl:
             type_ = "Suspend"
+        elif "http" in tmpl:
+            type_ = "HTTP"
         else:
             type_ = "Pod"
         node = self._open(node_id, display, type_, (tscope, tmpl.get("name"), target[2]), parent)
@@ -314,6 +325,8 @@ class WorkflowRun:
                 duration = substitute((tmpl["suspend"] or {}).get("duration", 0) or 0, scope)
                 await asyncio.sleep(parse_duration(duration))
                 ok, message = True, ""
+            elif type_ == "HTTP":
+                ok, message, outputs = await self._run_http(tmpl, scope, node)
             elif "container" in tmpl or "script" in tmpl:
                 ok, message, outputs = await self._run_leaf(tmpl, scope, node)
             else:
@@ -323,7 +336,7 @@ class WorkflowRun:
         except TemplateError as e:
             ok, message, outputs = False, str(e), None
         if ok and outputs:
-            self._export_globals(tmpl, outputs, leaf=type_ == "Pod")
+            self._export_globals(tmpl, outputs, leaf=type_ in ("Pod", "HTTP"))
         phase = "Succeeded" if ok else "Failed"
         self._close(node, phase, message, outputs)
         return phase, message, outputs if ok else None
@@ -598,8 +611,101 @@ class WorkflowRun:
             if workdir is not None:
                 shutil.rmtree(workdir, ignore_errors=True)
 
+    async def _run_http(self, tmpl: Dict[str, Any], scope: Scope,
+                        node: Dict[str, Any]) -> Tuple[bool, str, Optional[Outputs]]:
+        """One HTTP probe on the event loop: no process, so no slot of
+        ``spec.parallelism`` or of the engine's process bound. A cancellation
+        unwinds through the probe, which closes its socket first."""
+        from .httpprobe import ProbeError, Request, probe
+
+        body = tmpl["http"] or {}
+        url = str(substitute(to_str(body.get("url") or ""), scope))
+        method = str(substitute(to_str(body.get("method") or "GET"), scope))
+        headers = tuple(
+            (str(h["name"]), str(substitute(to_str(h["value"]), scope)))
+            for h in body.get("headers") or []
+            if isinstance(h, dict) and h.get("name") is not None and h.get("value") is not None
+        )
+        sent = body.get("body")
+        if sent is not None:
+            sent = str(substitute(to_str(sent), scope))
+        timeout = body.get("timeoutSeconds") or HTTP_DEFAULT_TIMEOUT_SECONDS
+        condition = None
+        if body.get("successCondition") is not None:
+            text = str(substitute(to_str(body["successCondition"]), scope))
+            try:
+                condition = parse_expr(text)
+            except ExprError as e:
+                return False, f"invalid successCondition: {e}", None
+
+        writer = self._log_writer(node)
+
+        def say(line: str) -> None:
+            if writer is not None:
+                writer.write(line.encode(errors="replace") + b"\n")
+
+        try:
+            if self._http_slots is not None:
+                await self._http_slots.acquire()
+            try:
+                response = await probe(Request(url, method, headers, sent),
+                                       timeout=float(timeout),
+                                       insecure=body.get("insecureSkipVerify") is True, log=say)
+            except ProbeError as e:
+                say(f"! {e}")
+                return False, str(e), None
+            finally:
+                if self._http_slots is not None:
+                    self._http_slots.release()
+            if writer is not None and response.body:
+                writer.write(response.body)
+        finally:
+            if writer is not None:
+                writer.close()
+
+        result = response.body.decode(errors="replace")
+        env = {"response": {"statusCode": response.status, "body": result,
+                            "headers": response.headers}}
+        if condition is None:
+            if response.status >= 300:
+                return False, f"received non-2xx response code: {response.status}", None
+        else:
+            try:
+                met = condition.evaluate_bool(env)
+            except ExprError as e:
+                return False, f"invalid successCondition: {e}", None
+            if not met:
+                return False, (f"successCondition {condition.text!r} evaluated false "
+                               f"(status {response.status})"), None
+        params: Dict[str, str] = {}
+        for p in (tmpl.get("outputs") or {}).get("parameters") or []:
+            if not isinstance(p, dict) or p.get("name") is None:
+                continue
+            value_from = p.get("valueFrom") if isinstance(p.get("valueFrom"), dict) else {}
+            default = value_from.get("default")
+            value: Any = None
+            if p.get("value") is not None:
+                value = substitute(to_str(p["value"]), scope)
+            elif value_from.get("expression") is not None:
+                try:
+                    found = parse_expr(
+                        str(substitute(to_str(value_from["expression"]), scope))
+                    ).evaluate(env)
+                    if found is None:
+                        raise ExprError("the value is nil")
+                    value = render_expr(found)
+                except ExprError as e:
+                    if default is None:
+                        return False, f"output parameter {p['name']!r}: {e}", None
+                    value = to_str(default)
+            elif default is not None:
+                value = to_str(default)
+            if value is not None:
+                params[str(p["name"])] = value
+        return True, "", {"result": result, "parameters": params}
+
     def _log_writer(self, node: Optional[Dict[str, Any]]) -> Any:
-        """The log writer of a Pod node, or None: without a store, or when
+        """The log writer of a leaf's node, or None: without a store, or when
         the store cannot take this run (the leaf runs all the same)."""
         if self.logs is None or node is None:
             return None

@@ -10,6 +10,8 @@ from __future__ import annotations
 import re
 from typing import Any, Dict, List, Optional, Set
 
+from .expr import FUNCTIONS, ExprError
+from .expr import parse as parse_expr
 from .template import find_refs, find_strings
 from .templates import (
     OWN_SCOPE,
@@ -25,9 +27,18 @@ from .templates import (
 )
 
 #: template body types the local executor runs
-BODY_TYPES = ("container", "script", "steps", "dag", "suspend")
+BODY_TYPES = ("container", "script", "steps", "dag", "suspend", "http")
 #: body types Argo knows that have no local equivalent
-UNSUPPORTED_BODY_TYPES = ("resource", "http", "data", "containerSet", "plugin")
+UNSUPPORTED_BODY_TYPES = ("resource", "data", "containerSet", "plugin")
+
+HTTP_METHODS = ("GET", "HEAD", "POST", "PUT", "PATCH", "DELETE", "OPTIONS")
+#: ``timeoutSeconds`` of an ``http`` template that sets none (Argo's default,
+#: from memory)
+HTTP_DEFAULT_TIMEOUT_SECONDS = 30
+_HTTP_KEYS = ("url", "method", "headers", "body", "timeoutSeconds", "successCondition",
+              "insecureSkipVerify")
+#: what an expression of an ``http`` template may name
+_HTTP_EXPR_NAMES = ("response", "response.statusCode", "response.body", "response.headers")
 
 _WORKFLOW_VARS = {"workflow.name", "workflow.namespace", "workflow.status"}
 _DEPENDS_RE = re.compile(r"^[A-Za-z0-9_\-]+(\s*&&\s*[A-Za-z0-9_\-]+)*$")
@@ -158,6 +169,67 @@ def ignored_synchronization(spec: Dict[str, Any],
     return found
 
 
+def _check_expression(where: str, what: str, text: Any, problems: List[str]) -> None:
+    """An expression of an ``http`` template: it parses and names only what
+    the executor gives it. One that still holds ``{{...}}`` is judged when it
+    runs; its references are checked like everywhere else."""
+    if not isinstance(text, str) or not text.strip():
+        problems.append(f"{where}: {what} must be a non-empty string")
+        return
+    if "{{" in text:
+        return
+    try:
+        names = parse_expr(text).names()
+    except ExprError as e:
+        problems.append(f"{where}: invalid {what}: {e}")
+        return
+    for name in sorted(names.identifiers):
+        if name not in _HTTP_EXPR_NAMES and not name.startswith("response.headers."):
+            problems.append(f"{where}: {what} uses the unknown name {name!r}")
+    for fn in sorted(names.functions - set(FUNCTIONS)):
+        problems.append(f"{where}: {what} calls the unknown function {fn!r}")
+
+
+def _check_http(where: str, tmpl: Dict[str, Any], problems: List[str]) -> None:
+    body = tmpl.get("http")
+    if not isinstance(body, dict):
+        problems.append(f"{where}: http is not a map")
+        return
+    if not isinstance(body.get("url"), str) or not body["url"].strip():
+        problems.append(f"{where}: http.url must be a non-empty string")
+    method = body.get("method")
+    if method is not None and "{{" not in str(method) and method not in HTTP_METHODS:
+        problems.append(
+            f"{where}: http.method {method!r} is not one of {', '.join(HTTP_METHODS)}")
+    headers = body.get("headers")
+    if headers is not None and not isinstance(headers, list):
+        problems.append(f"{where}: http.headers is not a list")
+    for h in headers if isinstance(headers, list) else []:
+        if isinstance(h, dict) and "valueFrom" in h:
+            problems.append(
+                f"{where}: http header {h.get('name')!r} has a valueFrom: "
+                "secret references have no local equivalent")
+        elif (not isinstance(h, dict) or not isinstance(h.get("name"), str) or not h["name"]
+              or not isinstance(h.get("value"), str) or set(h) - {"name", "value"}):
+            problems.append(f"{where}: http.headers entries must be {{name, value}} strings")
+    if "body" in body and not isinstance(body["body"], str):
+        problems.append(f"{where}: http.body must be a string")
+    if "timeoutSeconds" in body and not _positive_int(body["timeoutSeconds"]):
+        problems.append(f"{where}: http.timeoutSeconds must be a positive integer")
+    if "insecureSkipVerify" in body and not isinstance(body["insecureSkipVerify"], bool):
+        problems.append(f"{where}: http.insecureSkipVerify must be true or false")
+    for key in body:
+        if key not in _HTTP_KEYS:
+            problems.append(f"{where}: http.{key} is not supported")
+    if "successCondition" in body:
+        _check_expression(where, "successCondition", body["successCondition"], problems)
+    for p in (tmpl.get("outputs") or {}).get("parameters") or []:
+        value_from = p.get("valueFrom") if isinstance(p, dict) else None
+        if isinstance(value_from, dict) and "expression" in value_from:
+            _check_expression(where, f"outputs.parameters.{p.get('name')} expression",
+                              value_from["expression"], problems)
+
+
 UNRESOLVABLE = "cannot be resolved here: no WorkflowTemplates were given"
 
 
@@ -181,6 +253,9 @@ def _check_template(where: str, tmpl: Dict[str, Any], local: Dict[Any, Dict[str,
         problems.append(
             f"{where}: several bodies ({', '.join(bodies + foreign)}); expected exactly one"
         )
+
+    if "http" in tmpl:
+        _check_http(where, tmpl, problems)
 
     if tmpl.get("parallelism") is not None and not _positive_int(tmpl["parallelism"]):
         problems.append(f"{where}: parallelism must be a positive integer")
