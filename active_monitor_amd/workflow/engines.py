@@ -529,8 +529,8 @@ class LocalWorkflowEngine(_EngineBase):
       over all runs, and none of them counts against ``max_processes``;
     - ``steps`` (sequential groups of parallel steps) and ``dag`` templates
       (``dependencies`` / ``depends: "a && b"``, fail-fast by default);
-    - ``withItems`` / ``withParam`` fan-out and ``when`` conditions on steps
-      and tasks;
+    - ``withItems`` / ``withParam`` / ``withSequence`` fan-out, ``when``
+      conditions and ``continueOn: {failed: true}`` on steps and tasks;
     - parameters: ``spec.arguments``, template ``inputs``, ``{{item}}``,
       ``{{retries}}``, ``{{workflow.*}}`` and ``{{steps|tasks.X.outputs.*}}``,
       substituted in one pass and never re-split into argv elements;
@@ -547,7 +547,12 @@ class LocalWorkflowEngine(_EngineBase):
       admission reads the spec (:mod:`.templates`, :mod:`.template_cache`);
     - workflow-level ``activeDeadlineSeconds``. Every leaf runs in its own
       process group, which is killed when the deadline passes or the engine
-      stops.
+      stops;
+    - per-step deadlines, cut the same way: a template's
+      ``activeDeadlineSeconds`` bounds one attempt of a ``container`` or
+      ``script`` leaf from the start of its process, its ``timeout`` a
+      ``container``, ``script``, ``http`` or ``suspend`` node as a whole,
+      slot waits, retries and backoff waits included.
 
     The spec is checked by :func:`~.validate.validate_workflow_spec` before
     anything starts. Status is written twice per workflow (``Running``, then

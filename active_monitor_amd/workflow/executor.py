@@ -24,11 +24,14 @@ from .expr import render as render_expr
 from .template import (
     TemplateError,
     UnresolvedReference,
+    active_deadline,
     eval_when,
+    expand_sequence,
     item_display_name,
     item_scope,
     parse_duration,
     parse_with_param,
+    step_timeout,
     substitute,
     substitute_list,
     to_str,
@@ -55,6 +58,11 @@ _KILL_DRAIN_SECONDS = 1.0
 #: in the process table until then; the kill path waits this long for the
 #: group to be empty, so that a workflow reported Failed has left nothing
 _KILL_REAP_SECONDS = 5.0
+#: a leaf attempt that outran its template's ``activeDeadlineSeconds``
+#: (Argo's wording for the pod it would have been, from memory)
+POD_DEADLINE_MESSAGE = "Pod was active on the node longer than the specified deadline"
+#: a node that outran its template's ``timeout``, retries and waits included
+STEP_DEADLINE_MESSAGE = "Step exceeded its deadline"
 #: HTTP probes in flight at once, over all runs of an engine
 HTTP_MAX_IN_FLIGHT = 64
 
@@ -112,6 +120,13 @@ class Bound:
             if not fut.done():
                 self.held += 1
                 fut.set_result(None)
+
+
+def _continues(call: Dict[str, Any]) -> bool:
+    """Whether the caller of a step or task goes on when it failed. Only
+    ``continueOn.failed`` counts: no node here ever ends in ``Error``."""
+    on = call.get("continueOn")
+    return isinstance(on, dict) and on.get("failed") is True
 
 
 def _parallelism_bound(tmpl: Dict[str, Any]) -> Optional[Bound]:
@@ -258,6 +273,46 @@ class WorkflowRun:
     async def _run_template(self, target: Target, args: Dict[str, str], node_id: str,
                             display: str, parent: Optional[str], wf_scope: Scope) -> Result:
         tmpl = (self._scopes.get(target[0]) or {}).get(target[1]) or {}
+        if not tmpl.get("timeout"):  # none, 0 or "": nothing is put around it
+            return await self._run_attempts(tmpl, target, args, node_id, display, parent,
+                                            wf_scope)
+        try:
+            written = tmpl["timeout"]
+            budget = step_timeout(written, self._inputs(tmpl, args, wf_scope)
+                                  if isinstance(written, str) and "{{" in written else {})
+        except TemplateError as e:
+            message = f"invalid timeout: {e}"
+            self._mark(node_id, display, target, parent, "Failed", message)
+            return "Failed", message, None
+        attempts = self._run_attempts(tmpl, target, args, node_id, display, parent, wf_scope)
+        if budget is None:
+            return await attempts
+        try:
+            # the node as a whole: waits for a slot, every attempt and every
+            # backoff wait. On expiry the running attempt is cancelled and
+            # awaited, so its group is killed and reaped, its slots, directory
+            # and log writer are given back, before the node is reported
+            return await asyncio.wait_for(attempts, budget)
+        except asyncio.TimeoutError:
+            if node_id in self.nodes:
+                self._cut(node_id, STEP_DEADLINE_MESSAGE)
+            else:  # over before the first attempt could open it
+                self._mark(node_id, display, target, parent, "Failed", STEP_DEADLINE_MESSAGE)
+            return "Failed", STEP_DEADLINE_MESSAGE, None
+
+    def _cut(self, node_id: str, message: str) -> None:
+        """Close ``node_id`` and what is still open below it as ``Failed``."""
+        node = self.nodes.get(node_id)
+        if node is None:
+            return
+        for child in node["children"]:
+            self._cut(child, message)
+        if "phase" not in node:
+            self._close(node, "Failed", message)
+
+    async def _run_attempts(self, tmpl: Dict[str, Any], target: Target, args: Dict[str, str],
+                            node_id: str, display: str, parent: Optional[str],
+                            wf_scope: Scope) -> Result:
         retry = tmpl.get("retryStrategy")
         if not isinstance(retry, dict):
             return await self._run_once(tmpl, target, args, node_id, display, parent,
@@ -455,15 +510,21 @@ class WorkflowRun:
         calling template's ``parallelism``: the call, or each item of its
         loop, holds one slot of it from start to end. ``tscope`` is the
         calling template's scope, where a ``template:`` of the call is looked
-        up."""
+        up. A failure under ``continueOn: {failed: true}`` is published as
+        ``Failed`` and returned as a success."""
         name = str(call.get("name"))
         target = self._target(call, tscope)
+        # a failure that is continued past keeps its nodes and its status
+        # Failed, and reads as a success to the caller alone
+        continued: Result = ("Succeeded", "", None)
         try:
-            if "withItems" in call or "withParam" in call:
+            if "withItems" in call or "withParam" in call or "withSequence" in call:
                 if "withItems" in call:
                     items = call["withItems"]
                     if not isinstance(items, list):
                         raise TemplateError("withItems is not a list")
+                elif "withSequence" in call:
+                    items = expand_sequence(call["withSequence"], scope)
                 else:
                     items = parse_with_param(substitute(to_str(call["withParam"]), scope))
                 results = await _gather([
@@ -482,6 +543,8 @@ class WorkflowRun:
                 else:
                     phase = "Succeeded"
                 scope[f"{kind}.{name}.status"] = phase
+                if failed and _continues(call):
+                    return continued
                 return phase, failed[0] if failed else "", None
             phase, message, outputs = await self._run_expanded(
                 call, target, parent, node_id, name, scope, bound)
@@ -489,6 +552,8 @@ class WorkflowRun:
             self._mark(node_id, name, target, parent, "Failed", str(e))
             return "Failed", str(e), None
         scope[f"{kind}.{name}.status"] = phase
+        if phase == "Failed" and _continues(call):
+            return continued
         if phase == "Succeeded" and outputs:
             if outputs.get("result") is not None:
                 scope[f"{kind}.{name}.outputs.result"] = outputs["result"]
@@ -508,7 +573,7 @@ class WorkflowRun:
                 self._mark(node_id, display, target, parent, "Omitted", message)
                 return "Omitted", message, None
             result = await self._run_child(call, target, parent, node_id, display, scope)
-            if result[0] == "Failed" and bound.fail_fast:
+            if result[0] == "Failed" and bound.fail_fast and not _continues(call):
                 bound.closed = True  # before the slot goes to the next in line
             return result
         finally:
@@ -537,6 +602,10 @@ class WorkflowRun:
     async def _run_leaf(self, tmpl: Dict[str, Any], scope: Scope,
                         node: Dict[str, Any]) -> Tuple[bool, str, Optional[Outputs]]:
         stdin: Optional[bytes] = None
+        try:
+            deadline = active_deadline(tmpl.get("activeDeadlineSeconds"), scope)
+        except TemplateError as e:
+            return False, f"invalid activeDeadlineSeconds: {e}", None
         if "container" in tmpl:
             body = tmpl["container"] or {}
             cmd = substitute_list(body.get("command"), scope) + substitute_list(
@@ -573,7 +642,18 @@ class WorkflowRun:
                 for bound in self._process_bounds:
                     await bound.acquire()
                     held.append(bound)
-                ok, message, stdout = await self._exec(cmd, stdin, env, workdir, node)
+                if deadline is None:
+                    ok, message, stdout = await self._exec(cmd, stdin, env, workdir, node)
+                else:
+                    # the clock of one attempt starts with its process, not
+                    # with the wait for a slot. The cancellation that expiry
+                    # sends takes the kill path of _exec and is awaited, so
+                    # the group is gone and the log closed when this returns
+                    try:
+                        ok, message, stdout = await asyncio.wait_for(
+                            self._exec(cmd, stdin, env, workdir, node), deadline)
+                    except asyncio.TimeoutError:
+                        ok, message, stdout = False, POD_DEADLINE_MESSAGE, b""
             finally:
                 for bound in reversed(held):
                     bound.release()

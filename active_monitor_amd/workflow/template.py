@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import json
 import re
-from typing import Any, Dict, Iterator, List, Mapping, Tuple
+from typing import Any, Dict, Iterator, List, Mapping, Optional, Tuple
 
 REF_RE = re.compile(r"\{\{\s*([A-Za-z_][A-Za-z0-9_.\-]*)\s*\}\}")
 
@@ -121,6 +121,65 @@ def parse_with_param(text: str) -> List[Any]:
     return items
 
 
+#: a ``withSequence`` longer than this is refused: every item becomes a task
+#: at once, and a count this large on the machine under check is a typo
+SEQUENCE_MAX_ITEMS = 10_000
+_SEQUENCE_KEYS = ("count", "start", "end", "format")
+_INTEGER = re.compile(r"[+-]?\d+$")
+#: literal text, one verb out of d x X o with an optional zero-padded width,
+#: literal text
+_SEQUENCE_FORMAT = re.compile(r"([^%]*)%((?:0\d+)?[dxXo])([^%]*)$")
+
+
+def _sequence_int(key: str, value: Any) -> int:
+    if isinstance(value, int) and not isinstance(value, bool):
+        return value
+    if isinstance(value, str) and _INTEGER.match(value.strip()):
+        return int(value.strip())
+    raise TemplateError(f"withSequence.{key} {value!r} is not an integer")
+
+
+def expand_sequence(seq: Any, scope: Mapping[str, str] = {}) -> List[str]:
+    """The items of a ``withSequence``, as strings: ``count`` of them from
+    ``start`` (default 0) upwards, or ``start`` to ``end`` inclusive, counting
+    down when ``end`` is the smaller. ``{{...}}`` in a field is resolved in
+    ``scope`` first. ``format`` is checked against the one shape it may have
+    and is never handed to ``%`` as it came."""
+    if not isinstance(seq, dict):
+        raise TemplateError("withSequence is not a map")
+    for key in seq:
+        if key not in _SEQUENCE_KEYS:
+            raise TemplateError(f"withSequence.{key} is not supported")
+    given = {k: substitute(v, scope) for k, v in seq.items() if v is not None}
+    if "count" in given and "end" in given:
+        raise TemplateError("withSequence takes count or end, not both")
+    if "count" not in given and "end" not in given:
+        raise TemplateError("withSequence needs count or end")
+    start = _sequence_int("start", given["start"]) if "start" in given else 0
+    if "count" in given:
+        count = _sequence_int("count", given["count"])
+        if count < 0:
+            raise TemplateError(f"withSequence.count {count} is negative")
+        step = 1
+    else:
+        end = _sequence_int("end", given["end"])
+        count = abs(end - start) + 1
+        step = 1 if end >= start else -1
+    if count > SEQUENCE_MAX_ITEMS:
+        raise TemplateError(
+            f"withSequence expands to {count} items, more than the cap of "
+            f"{SEQUENCE_MAX_ITEMS}")
+    prefix, verb, suffix = "", "d", ""
+    if "format" in given:
+        m = _SEQUENCE_FORMAT.match(given["format"]) if isinstance(given["format"], str) else None
+        if m is None:
+            raise TemplateError(
+                f"withSequence.format {given['format']!r} is not one of %d, %x, %X, %o "
+                "(with an optional zero-padded width) inside literal text")
+        prefix, verb, suffix = m.groups()
+    return [prefix + format(start + i * step, verb) + suffix for i in range(count)]
+
+
 # -- durations ------------------------------------------------------------
 
 _DURATION_PART = re.compile(r"(\d+(?:\.\d*)?|\.\d+)(ms|s|m|h)")
@@ -151,6 +210,35 @@ def parse_duration(value: Any) -> float:
     if seconds < 0 or seconds != seconds or seconds == float("inf"):
         raise TemplateError(f"invalid duration {value!r}")
     return seconds
+
+
+def step_timeout(value: Any, scope: Mapping[str, str] = {}) -> Optional[float]:
+    """Seconds of a template's ``timeout``; None when it sets none, which is
+    how zero and the empty string read as well. A ``{{...}}`` reference is
+    resolved in ``scope`` and then has to give a positive duration."""
+    if value is None or value == "" or (not isinstance(value, bool) and value == 0):
+        return None
+    resolved = substitute(value, scope)
+    seconds = parse_duration(resolved)
+    if seconds > 0:
+        return seconds
+    if resolved is value:
+        return None  # zero in another spelling: 0s
+    raise TemplateError(f"{resolved!r} is not a positive duration")
+
+
+def active_deadline(value: Any, scope: Mapping[str, str] = {}) -> Optional[float]:
+    """Seconds of a template's ``activeDeadlineSeconds``; None when it sets
+    none. A positive integer, as a number or as a string, once a ``{{...}}``
+    reference is resolved in ``scope``."""
+    if value is None:
+        return None
+    resolved = substitute(value, scope)
+    if isinstance(resolved, str) and _INTEGER.match(resolved.strip()):
+        resolved = int(resolved.strip())
+    if isinstance(resolved, bool) or not isinstance(resolved, int) or resolved < 1:
+        raise TemplateError(f"{resolved!r} is not a positive integer")
+    return float(resolved)
 
 
 # -- when -----------------------------------------------------------------

@@ -12,7 +12,15 @@ from typing import Any, Dict, List, Optional, Set
 
 from .expr import FUNCTIONS, ExprError
 from .expr import parse as parse_expr
-from .template import find_refs, find_strings
+from .template import (
+    REF_RE,
+    TemplateError,
+    active_deadline,
+    expand_sequence,
+    find_refs,
+    find_strings,
+    step_timeout,
+)
 from .templates import (
     OWN_SCOPE,
     Lookup,
@@ -99,8 +107,9 @@ def _find_cycle(deps: Dict[str, List[str]]) -> Optional[str]:
 def _check_refs(where: str, obj: Any, inputs: Set[str], wf_params: Optional[Set[str]],
                 call_names: Set[str], kind: str, problems: List[str],
                 in_loop: bool = False) -> None:
-    """``in_loop``: ``obj`` is a step or task that carries ``withItems`` /
-    ``withParam`` — the only place where ``{{item}}`` means anything.
+    """``in_loop``: ``obj`` is a step or task that carries ``withItems``,
+    ``withParam`` or ``withSequence`` — the only place where ``{{item}}``
+    means anything.
     ``wf_params`` None: workflow parameters are not known here (a template
     document checked on its own) and any name passes."""
     for text in find_strings(obj):
@@ -230,6 +239,53 @@ def _check_http(where: str, tmpl: Dict[str, Any], problems: List[str]) -> None:
                               value_from["expression"], problems)
 
 
+_LOOP_KEYS = ("withItems", "withParam", "withSequence")
+
+
+def _check_sequence(where: str, seq: Any, problems: List[str]) -> None:
+    """Expand it once, with a zero in place of every ``{{...}}``: a number
+    that is a reference is judged when it runs, the shape and whatever is
+    written out are judged here. A ``format`` with a reference is left out."""
+    if isinstance(seq, dict):
+        seq = {k: REF_RE.sub("0", v) if isinstance(v, str) else v for k, v in seq.items()
+               if not (k == "format" and isinstance(v, str) and "{{" in v)}
+    try:
+        expand_sequence(seq)
+    except TemplateError as e:
+        problems.append(f"{where}: {e}")
+
+
+def _check_continue_on(where: str, on: Any, problems: List[str]) -> None:
+    if not isinstance(on, dict):
+        problems.append(f"{where}: continueOn is not a map")
+        return
+    for key, value in on.items():
+        if key not in ("failed", "error"):
+            problems.append(f"{where}: continueOn.{key} is not supported (failed, error)")
+        elif not isinstance(value, bool):
+            problems.append(f"{where}: continueOn.{key} must be true or false")
+
+
+def _check_deadlines(where: str, tmpl: Dict[str, Any], problems: List[str]) -> None:
+    """``timeout`` and ``activeDeadlineSeconds`` of a template. A value that
+    holds ``{{...}}`` is judged when it runs."""
+    if "timeout" in tmpl:
+        value = tmpl["timeout"]
+        if "steps" in tmpl or "dag" in tmpl:
+            problems.append(f"{where}: timeout is not supported on steps and dag templates")
+        elif not (isinstance(value, str) and "{{" in value):
+            try:
+                step_timeout(value)
+            except TemplateError as e:
+                problems.append(f"{where}: invalid timeout: {e}")
+    value = tmpl.get("activeDeadlineSeconds")
+    if not (isinstance(value, str) and "{{" in value):
+        try:
+            active_deadline(value)
+        except TemplateError as e:
+            problems.append(f"{where}: invalid activeDeadlineSeconds: {e}")
+
+
 UNRESOLVABLE = "cannot be resolved here: no WorkflowTemplates were given"
 
 
@@ -259,6 +315,7 @@ def _check_template(where: str, tmpl: Dict[str, Any], local: Dict[Any, Dict[str,
 
     if tmpl.get("parallelism") is not None and not _positive_int(tmpl["parallelism"]):
         problems.append(f"{where}: parallelism must be a positive integer")
+    _check_deadlines(where, tmpl, problems)
 
     calls = calls_of(tmpl)
     kind = "tasks" if "dag" in tmpl else ("steps" if "steps" in tmpl else "")
@@ -280,11 +337,13 @@ def _check_template(where: str, tmpl: Dict[str, Any], local: Dict[Any, Dict[str,
                 problems.append(f"{cwhere}: templateRef {UNRESOLVABLE}")
         elif call.get("template") not in local:
             problems.append(f"{cwhere}: template {call.get('template')!r} not found")
-        for key in ("withSequence", "continueOn"):
-            if key in call:
-                problems.append(f"{cwhere}: {key} is not supported")
-        if "withItems" in call and "withParam" in call:
-            problems.append(f"{cwhere}: withItems and withParam are mutually exclusive")
+        loops = [key for key in _LOOP_KEYS if key in call]
+        if len(loops) > 1:
+            problems.append(f"{cwhere}: {' and '.join(loops)} are mutually exclusive")
+        if "withSequence" in call:
+            _check_sequence(cwhere, call["withSequence"], problems)
+        if "continueOn" in call:
+            _check_continue_on(cwhere, call["continueOn"], problems)
         if "withItems" in call and not isinstance(call["withItems"], list):
             problems.append(f"{cwhere}: withItems is not a list")
 
@@ -317,7 +376,7 @@ def _check_template(where: str, tmpl: Dict[str, Any], local: Dict[Any, Dict[str,
     for call in calls:
         _check_refs(f"{where}: {kind[:-1]} {call.get('name')!r}", call, inputs, wf_params,
                     names, kind, problems,
-                    in_loop="withItems" in call or "withParam" in call)
+                    in_loop=any(key in call for key in _LOOP_KEYS))
 
 
 def _named_templates(spec: Dict[str, Any], where: str,
